@@ -11,11 +11,19 @@ partition, gamma (leaf value) pass and prediction update — nothing skipped.
 The total data size is fixed (strong scaling): with N GPUs every rank holds
 100M/N rows and histograms are reduce-scattered over RCCL.
 
-The GLM half of the headline metric (GLM binomial IRLSM iterations/s on the
-same frame) is measured after the GBM steps and reported as extra keys
-(glm_iters_per_sec, glm_ms_per_iter) of the same JSON line; --no-glm skips it.
+A plain run sets up, warms up, times the steps and prints one JSON result
+line.  --dump-outputs DIR also writes what the last timed step left for its
+caller as DIR/<name>.npy (the inputs are seeded, so two builds can be compared
+output for output).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--algo gbm|glm|drf] [--no-glm]
+--full adds everything else to the same JSON line: the training-quality and
+convergence sanity figures, and the GLM half of the headline metric (GLM
+binomial IRLSM iterations/s on the same frame, measured after the GBM steps
+and reported as the extra keys glm_iters_per_sec, glm_ms_per_iter; --no-glm
+skips it).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--algo gbm|glm|drf] [--full [--no-glm]]
+       [--dump-outputs DIR]
        [--cols C] [--cat-cols K --cat-card L]   (DRF config: --algo drf --rows 50000000 --cols 500 --cat-cols 100)
 """
 import argparse
@@ -84,6 +92,29 @@ def make_frame(args, dev, rank, rows_local):
     return fr, names, y
 
 
+_DUMP_BYTES = 48_000_000   # all files of --dump-outputs together stay below 64 MB
+
+
+def dump_outputs(d, outs):
+    """Write every array of outs as d/<name>.npy, float64 where it is float64
+    and float32 otherwise.  An array above its share of _DUMP_BYTES is cut to
+    a fixed sample of its flattened elements (seeded, sorted positions), the
+    same positions in every run of the same shape."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    share = _DUMP_BYTES // max(len(outs), 1)
+    for name, a in outs.items():
+        t = a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = share // (8 if dt == torch.float64 else 4)
+        if t.numel() > cap:
+            g = torch.Generator(device="cpu").manual_seed(987654321)
+            pos = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[pos.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.to(dt).cpu().numpy())
+
+
 def _launch(n):
     """Run this script on n ranks (one process per GPU) under
     torch.distributed.run on 127.0.0.1 and return its exit status."""
@@ -119,9 +150,15 @@ def main():
     ap.add_argument("--cat-card", type=int, default=1000, help="cardinality of the categorical columns")
     ap.add_argument("--histogram-type", default="QuantilesGlobal")
     ap.add_argument("--nbins", type=int, default=255)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the training-quality / convergence "
+                         "sanity figures and, with --algo gbm, the companion GLM measurement")
     ap.add_argument("--no-glm", action="store_true",
-                    help="--algo gbm: skip the companion GLM measurement (the headline metric is GBM trees/s + "
-                         "GLM iters/s on the same 100M x 100 frame; the GLM figure is reported as extra keys)")
+                    help="--full --algo gbm: skip the companion GLM measurement (the headline metric is GBM trees/s "
+                         "+ GLM iters/s on the same 100M x 100 frame; the GLM figure is reported as extra keys)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32 / "
+                         "float64, below 64 MB in all; a fixed seeded sample of a larger array; rank 0's shard)")
     args = ap.parse_args()
 
     ws = os.environ.get("WORLD_SIZE")
@@ -157,6 +194,9 @@ def main():
         est._spec = spec
         drv = GBMDriver(est, spec)
         step = drv.step
+
+        def outputs():
+            return {"predictions": drv.predictions()}
         metric = "gbm_trees_per_sec"
         unit = "trees/s"
         model = f"GBM binomial {args.rows / 1e6:g}Mx{F} ntrees=500 max_depth={args.max_depth}"
@@ -169,6 +209,9 @@ def main():
         est._spec = spec
         drv = DRFDriver(est, spec)
         step = drv.step
+
+        def outputs():
+            return {"oob_sum": drv.oob_sum, "oob_count": drv.oob_cnt}
         metric = "drf_trees_per_sec"
         unit = "trees/s"
         model = f"DRF binomial {args.rows // 1_000_000}Mx{F} ({args.cat_cols} cat, card {args.cat_card}) ntrees=1000"
@@ -192,6 +235,9 @@ def main():
             st = cluster_ops.lloyd_pass(Xk, C[0], None, asg, xabs_max=xabs)
             coll.allreduce_(st.vec)
             C[0] = torch.where(st.weights.view(-1, 1) > 0, st.sums / st.weights.clamp_min(1e-300).view(-1, 1), C[0])
+
+        def outputs():
+            return {"centers": C[0], "assignments": asg}
         metric = "kmeans_iters_per_sec"
         unit = "iters/s"
         model = f"KMeans k={args.k} {args.rows / 1e6:g}Mx{F}"
@@ -213,6 +259,7 @@ def main():
         del fr
         P = di.P
         kk = args.k
+        last = {}
 
         def step():
             G, mu, nrow = gram_and_mean(Xp, P)
@@ -220,7 +267,11 @@ def main():
             ev, V = _top_eig(cov, kk, "randomized", 30, 1)
             Vp = torch.zeros((Xp.shape[1], V.shape[1]), dtype=torch.float64)
             Vp[:P] = V
-            cluster_ops.xv(Xp, Vp, min_rows=0)
+            last["eigenvalues"], last["eigenvectors"] = ev, V
+            last["projection"] = cluster_ops.xv(Xp, Vp, min_rows=0)
+
+        def outputs():
+            return last
         metric = "pca_fits_per_sec"
         unit = "fits/s"
         model = f"PCA Randomized k={args.k} {args.rows / 1e6:g}Mx{F} (Gram pass + subspace iterations + projections)"
@@ -252,6 +303,12 @@ def main():
                 gstep["g"].replay()
             else:
                 est._train_step(Xd.index_select(0, idx), Yd.index_select(0, idx), None, 1000, hp)
+
+        def outputs():
+            o = {}
+            for i, L in enumerate(est._layers):
+                o[f"W{i}"], o[f"b{i}"] = L.W, L.b
+            return o
         metric = "dl_samples_per_sec"
         unit = "samples/s"
         model = f"DeepLearning MLP {args.cols}-{args.hidden}-2 RectifierWithDropout, batch {args.batch}"
@@ -266,6 +323,9 @@ def main():
         est._spec = spec
         drv = GLMDriver(est, spec)
         step = drv.step
+
+        def outputs():
+            return {"beta": drv.beta}
         metric = "glm_iters_per_sec"
         unit = "iters/s"
         model = f"GLM binomial IRLSM {args.rows / 1e6:g}Mx{F}" + \
@@ -293,8 +353,10 @@ def main():
     value = args.steps / el
     if args.algo == "dl":
         value = args.steps * args.batch * world / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs())
     extra = {}
-    if args.algo == "gbm":
+    if args.algo == "gbm" and args.full:
         # training-quality sanity (not timed): logloss of the boosted model so far
         import math
         p = drv.predictions().clamp(1e-7, 1 - 1e-7)
@@ -303,15 +365,18 @@ def main():
         extra["train_logloss_after"] = round(ll, 5)
         extra["trees_built"] = len(drv.forest)
     if args.algo == "glm":
+        # the config states the Hessian tier the timed iterations ended on
+        tier = getattr(drv, "_hprec", None) or ("f64" if dev.type == "cpu" else None)
+        extra_cfg["gram_precision"] = _glm_precision(tier)
+    if args.algo == "glm" and args.full:
         # convergence sanity (not timed): deviance of the last iteration and the
         # final coefficient step
         extra["train_deviance_per_row"] = round(float(drv.last_dev) / float(drv.wsum), 6)
         extra["iters"] = int(drv.iter)
-        extra["hessian_tier"] = getattr(drv, "_hprec", None) or ("f64" if dev.type == "cpu" else None)
-        extra_cfg["gram_precision"] = _glm_precision(extra["hessian_tier"])
+        extra["hessian_tier"] = tier
         k_ = getattr(drv, "hessian_kappa", None)
         extra["hessian_kappa"] = None if k_ is None else round(float(k_), 3)
-    if args.algo == "gbm" and not args.no_glm:
+    if args.algo == "gbm" and args.full and not args.no_glm:
         # companion half of the headline metric: GLM binomial IRLSM iterations/s
         # on the SAME frame, timed separately with the same barrier + sync
         # discipline (the GBM value / ms_per_step above are not affected)

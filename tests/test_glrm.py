@@ -2,6 +2,7 @@
 categorical losses, imputation."""
 import numpy as np
 import pandas as pd
+import pytest
 
 import h2o3_amd as h2o
 from h2o3_amd.estimators import H2OGeneralizedLowRankEstimator
