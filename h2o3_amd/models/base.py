@@ -805,7 +805,8 @@ class H2OEstimator:
         raise ValueError(f"{self.algo}: staged predictions are only available for tree models")
 
     def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None,
-                              compare_abs=False, **kw):
+                              compare_abs=False, background_frame=None, output_space=False,
+                              output_per_reference=False):
         raise ValueError(f"{self.algo}: contributions (SHAP) are only available for tree models")
 
     def feature_frequencies(self, test_data):

@@ -184,7 +184,7 @@ def shap_summary_plot(model, frame, columns=None, top_n_features=20, samples=100
     fr = frame
     if samples and frame.nrows > samples:
         fr = frame.split_frame(ratios=[samples / frame.nrows], seed=42)[0]
-    contr = model.predict_contributions(fr).as_data_frame()
+    contr = model.predict_contributions(fr, background_frame=background_frame).as_data_frame()
     contr = contr[[c for c in contr.columns if c != "BiasTerm"]]
     imp = contr.abs().mean().sort_values(ascending=False)
     cols = list(imp.index[:top_n_features]) if columns is None else list(columns)
@@ -214,10 +214,10 @@ def shap_summary_plot(model, frame, columns=None, top_n_features=20, samples=100
 
 
 def shap_explain_row_plot(model, frame, row_index, columns=None, top_n_features=10, figsize=(16, 9),
-                          plot_type="barplot", contribution_type="both", save_plot_path=None):
+                          plot_type="barplot", contribution_type="both", save_plot_path=None, background_frame=None):
     plt = _plt()
     row = frame[int(row_index), :]
-    contr = model.predict_contributions(row).as_data_frame().iloc[0]
+    contr = model.predict_contributions(row, background_frame=background_frame).as_data_frame().iloc[0]
     bias = float(contr.get("BiasTerm", 0.0))
     contr = contr.drop(labels=[c for c in contr.index if c == "BiasTerm"])
     order = contr.abs().sort_values(ascending=False).index[:top_n_features] if columns is None else list(columns)

@@ -331,11 +331,15 @@ class H2OGenericEstimator(H2OEstimator):
 
     # ------------------------------------------------------------ tree extras
     def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None,
-                              compare_abs=False, **kw):
+                              compare_abs=False, background_frame=None, output_space=False,
+                              output_per_reference=False):
         """TreeSHAP of the imported trees on the device (GenericModel.java:449:
-        the MOJO's contribution predictor), same output layout as the MOJO's."""
+        the MOJO's contribution predictor), same output layout as the MOJO's.
+        With a background frame: baseline SHAP against its rows."""
         if self._forest is None:
             raise ValueError(f"contributions are not available for a {self._mojo.algo} MOJO")
+        if background_frame is None and (output_space or output_per_reference):
+            raise ValueError("output_space and output_per_reference can only be used with a background_frame")
         if self._ncls > 2:
             raise ValueError("Calculating contributions is currently not supported for multinomial models.")
         from .tree.shap import forest_contributions
@@ -343,6 +347,9 @@ class H2OGenericEstimator(H2OEstimator):
         F = len(self._x)
         trees = [t for t, k in zip(self._forest.trees, self._forest.tclass) if k == 0]
         algo = self._mojo.algo
+        if background_frame is not None:
+            return self._background_contributions(test_data, X, background_frame, top_n, bottom_n, compare_abs,
+                                                  output_space, output_per_reference)
         if algo in ("gbm", "xgboost"):
             phi = forest_contributions(trees, X, F)
             phi[:, -1] += float(self._init_f[0])
@@ -356,6 +363,37 @@ class H2OGenericEstimator(H2OEstimator):
         from ..mojo.treeshap_np import contributions_frame
         df = contributions_frame(phi.cpu().numpy(), self._x, top_n=top_n, bottom_n=bottom_n,
                                  compare_abs=compare_abs)
+        return H2OFrame(df, _local=True)
+
+    def _background_contributions(self, test_data, X, background_frame, top_n, bottom_n, compare_abs,
+                                  output_space, output_per_reference):
+        from .tree.shap import _gather_background, background_contributions
+        F = len(self._x)
+        Z = _gather_background(self._score_matrix(background_frame))
+        if Z.shape[1] == 0:
+            raise ValueError("background_frame has no rows")
+        if self._mojo.algo in ("gbm", "xgboost"):
+            link = self._link
+            linkinv = torch.sigmoid if link == "logit" else (torch.exp if link == "log" else (lambda f: f))
+            phi = background_contributions(self._forest, X, Z, F, bias=float(self._init_f[0]), linkinv=linkinv,
+                                           output_space=output_space, output_per_reference=output_per_reference)
+        else:
+            if self._K > 1:
+                raise ValueError("Calculating contributions with a background frame is not supported for DRF "
+                                 "with binomial_double_trees.")
+            nt = max(1, len(self._forest))
+            # trees of a reference binomial DRF MOJO score P(class 0): explain 1 - their mean
+            p0 = self._ncls == 2 and self._binomial_single and self._p0_trees
+            phi = background_contributions(self._forest, X, Z, F, vscale=(-1.0 if p0 else 1.0) / nt,
+                                           bias=1.0 if p0 else 0.0, output_per_reference=output_per_reference)
+        from ..mojo.treeshap_np import contributions_frame
+        df = contributions_frame(phi.cpu().numpy(), self._x, top_n=top_n, bottom_n=bottom_n,
+                                 compare_abs=compare_abs)
+        if output_per_reference:
+            B = Z.shape[1]
+            rows = np.arange(X.shape[1], dtype=np.int64) + test_data.row_offset()
+            df["RowIdx"] = np.repeat(rows, B)
+            df["BackgroundRowIdx"] = np.tile(np.arange(B, dtype=np.int64), X.shape[1])
         return H2OFrame(df, _local=True)
 
     def predict_leaf_node_assignment(self, test_data, type="Path"):

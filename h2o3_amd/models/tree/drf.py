@@ -162,9 +162,12 @@ class H2ORandomForestEstimator(SharedTreeEstimator):
         return self._normalize(sums / ntrees)
 
     def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None,
-                              compare_abs=False, background_frame=None):
+                              compare_abs=False, background_frame=None, output_space=False,
+                              output_per_reference=False):
         from .shap import tree_contributions
-        return tree_contributions(self, test_data, top_n=top_n, bottom_n=bottom_n, compare_abs=compare_abs)
+        return tree_contributions(self, test_data, top_n=top_n, bottom_n=bottom_n, compare_abs=compare_abs,
+                                  background_frame=background_frame, output_space=output_space,
+                                  output_per_reference=output_per_reference)
 
     def _score_all(self, spec):
         raw = self._predict_raw(spec.frame)

@@ -12,6 +12,10 @@ weights), so each EXTEND / UNWIND step is a handful of elementwise kernels
 over all rows at once instead of a per-row recursion.  Both children are
 visited with one-fraction = "row goes this way" (0/1 per row), which is
 the vectorised form of the reference's hot/cold recursion.
+
+With a background frame (`background_frame=`) the contributions are baseline
+(interventional) SHAP instead: recursion-free over leaf paths, work = test
+rows x background rows x leaves, on the HIP kernels of ops/shap_ops.py.
 """
 from __future__ import annotations
 
@@ -131,18 +135,93 @@ def forest_contributions(trees, X: torch.Tensor, F: int, scale: float = 1.0) -> 
     return phi
 
 
-def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=False):
+def background_contributions(forest, X, Z, F, vscale=1.0, bias=0.0, linkinv=None, output_space=False,
+                             output_per_reference=False, max_scratch_bytes=1 << 30):
+    """Baseline (interventional) SHAP of `forest`'s class-0 trees for the test
+    rows X [F, N] against the background rows Z [F, B] (ops/shap_ops.py: HIP
+    kernels on the GPU).  The link-space score of a row is bias + vscale *
+    (sum of its leaves).  Returns [N, F+1] f64 (mean over the background
+    rows) or [N*B, F+1] (one row per pair, test row major); the last column
+    is the bias term f(z), or linkinv(f(z)) with output_space, which also
+    rescales each pair's contributions to sum to linkinv(f(x)) - linkinv(f(z))."""
+    from ...ops import shap_ops
+    P = forest.pack(X.device)
+    PT = forest.leaf_paths(X.device)
+    B = Z.shape[1]
+    scale = None
+    if output_space and linkinv is not None:
+        def scale(fx, fz):
+            d = fx.view(-1, 1) - fz.view(1, -1)
+            g = linkinv(fx + bias).view(-1, 1) - linkinv(fz + bias).view(1, -1)
+            return torch.where(d == 0, torch.zeros_like(d), g / torch.where(d == 0, torch.ones_like(d), d))
+    res = shap_ops.background_shap(P, PT, X, Z, F, per_reference=output_per_reference, vscale=vscale,
+                                   pair_scale=scale, max_scratch_bytes=max_scratch_bytes)
+    phi = res.phi
+    bz = res.fz + bias
+    if scale is not None:
+        bz = linkinv(bz)
+    if output_per_reference:
+        phi.view(-1, B, F + 1)[:, :, F] = bz.view(1, B)
+    else:
+        phi[:, F] = bz.mean()
+    return phi
+
+
+def _gather_background(Z):
+    """Every rank gets all background rows ([F, B], rank order)."""
+    from ...parallel import cloud, collectives as coll
+    if not cloud.is_distributed():
+        return Z
+    return coll.all_gather_var(Z.t().contiguous()).t().contiguous()
+
+
+def _pair_index_vecs(frame, n_local, B, device):
+    """RowIdx / BackgroundRowIdx (global row numbers) of per-reference output."""
+    from ...core.vec import Vec, T_INT
+    rows = torch.arange(n_local, dtype=torch.float64, device=device) + float(frame.row_offset())
+    return [Vec(rows.repeat_interleave(B).contiguous(), T_INT),
+            Vec(torch.arange(B, dtype=torch.float64, device=device).repeat(n_local).contiguous(), T_INT)]
+
+
+def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=False, background_frame=None,
+                       output_space=False, output_per_reference=False):
     """predict_contributions for GBM / XGBoost / DRF (regression + binomial),
-    in link space like the reference: row sum == raw margin prediction."""
+    in link space like the reference: row sum == raw margin prediction.
+    With a background frame: baseline SHAP against its rows (bias term = mean
+    background prediction) instead of path-dependent TreeSHAP."""
     from ...core.frame import H2OFrame
     from ...core.vec import Vec, T_REAL, make_enum_from_strings
     spec = model._spec
+    if background_frame is None:
+        if output_space:
+            raise ValueError("output_space can only be used with a background_frame")
+        if output_per_reference:
+            raise ValueError("output_per_reference can only be used with a background_frame")
     if spec.nclasses > 2:
         raise ValueError("Calculating contributions is currently not supported for multinomial models.")
     X = model._score_matrix(frame)
     names = list(spec.x)
     trees = [t for t, k in zip(model._forest.trees, model._forest.tclass) if k == 0]
-    if model.algo == "drf":
+    extra = []
+    if background_frame is not None:
+        if model.algo == "drf" and model._n_tree_classes() > 1:
+            raise ValueError("Calculating contributions with a background frame is not supported for DRF "
+                             "with binomial_double_trees.")
+        Z = _gather_background(model._score_matrix(background_frame))
+        if Z.shape[1] == 0:
+            raise ValueError("background_frame has no rows")
+        if model.algo == "drf":
+            # the forest mean itself: P(class 1) (single-tree binomial) or the prediction
+            phi = background_contributions(model._forest, X, Z, len(names), vscale=1.0 / max(1, len(trees)),
+                                           output_per_reference=output_per_reference)
+        else:
+            phi = background_contributions(model._forest, X, Z, len(names), bias=float(model._init_f[0]),
+                                           linkinv=model._dist.linkinv, output_space=output_space,
+                                           output_per_reference=output_per_reference)
+        if output_per_reference:
+            extra = list(zip(_pair_index_vecs(frame, X.shape[1], Z.shape[1], X.device),
+                             ["RowIdx", "BackgroundRowIdx"]))
+    elif model.algo == "drf":
         phi = forest_contributions(trees, X, len(names), scale=1.0 / max(1, len(trees)))
         if spec.nclasses == 2:
             # the reference's binomial DRF form (ScoreContributionsTaskDRF,
@@ -156,7 +235,7 @@ def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=Fals
         phi[:, -1] += float(model._init_f[0])
     if top_n is None and bottom_n is None:
         vecs = [Vec(phi[:, j].to(torch.float32).contiguous(), T_REAL) for j in range(phi.shape[1])]
-        return H2OFrame.from_vecs(vecs, names + ["BiasTerm"])
+        return H2OFrame.from_vecs(vecs + [v for v, _ in extra], names + ["BiasTerm"] + [n for _, n in extra])
     # sorted output: top_feature_i / top_value_i (+ bottom_*), BiasTerm last
     c = phi[:, :-1]
     key = c.abs() if compare_abs else c
@@ -179,4 +258,7 @@ def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=Fals
         out_names += [f"bottom_feature_{i + 1}", f"bottom_value_{i + 1}"]
     cols.append(Vec(phi[:, -1].to(torch.float32).contiguous(), T_REAL))
     out_names.append("BiasTerm")
+    for v, n in extra:
+        cols.append(v)
+        out_names.append(n)
     return H2OFrame.from_vecs(cols, out_names)

@@ -87,6 +87,7 @@ class Forest:
         self.trees: list[Tree] = []
         self.tclass: list[int] = []
         self._packed = None
+        self._paths = None
 
     def add(self, tree: Tree, k: int = 0):
         self.trees.append(tree)
@@ -160,6 +161,109 @@ class Forest:
              "T": len(trees)}
         self._packed = (key, P)
         return P
+
+    def leaf_paths(self, device, upto=None):
+        """Leaf-path table for baseline SHAP (ops/shap_ops.py), cached and
+        invalidated like pack().  Leaves are numbered tree by tree; per leaf:
+        its value (f64), its tree's class, and its path elements (one per
+        distinct feature on the root-to-leaf path, ordered by feature id).
+        An element's conditions are (packed node index, wants-left) pairs
+        into pack()'s node arrays, so thresholds, NA directions and the
+        categorical bitsets are read from there.
+
+        Keys: leaf_val [L] f64, leaf_cls [L] i32, el_off [L+1], el_feat [E],
+        cond_off [E+1], cond_node [C] i32, cond_left [C] u8, tree_leaf_off
+        (host list, T+1), L, max_path (most elements of one leaf),
+        max_tree_leaves, max_feat (largest feature id split on, -1 if none)."""
+        trees = self.trees if upto is None else self.trees[:upto]
+        # keyed on the pack it indexes into: whatever drops the pack drops this too
+        P = self.pack(device, upto)
+        cached = self.__dict__.get("_paths")
+        if cached is not None and cached[0] is P:
+            return cached[1]
+        # vectorised per tree: walk every leaf up to the root one level per step
+        lval, lcls, nel, efeat, ncond, cnode, cleft = [], [], [], [], [], [], []
+        tree_leaf_off = [0]
+        base = 0
+        for ti, t in enumerate(trees):
+            n = t.n_nodes
+            l_ = np.asarray(t.left, dtype=np.int64)
+            r_ = np.asarray(t.right, dtype=np.int64)
+            f_ = np.asarray(t.feat, dtype=np.int64)
+            idx = np.arange(n, dtype=np.int64)
+            inner = l_ >= 0
+            parent = np.full(n, -1, dtype=np.int64)
+            isleft = np.zeros(n, dtype=np.uint8)
+            parent[l_[inner]] = idx[inner]
+            isleft[l_[inner]] = 1
+            parent[r_[inner]] = idx[inner]
+            leaves = idx[~inner]
+            cur = leaves.copy()
+            who = np.arange(leaves.size, dtype=np.int64)
+            c_leaf, c_node, c_left = [], [], []
+            top = leaves.copy()                       # highest ancestor reached
+            for _ in range(n):
+                p = parent[cur]
+                live = p >= 0
+                if not live.any():
+                    break
+                who, cur, p = who[live], cur[live], p[live]
+                c_leaf.append(who)
+                c_node.append(p)
+                c_left.append(isleft[cur])
+                top[who] = p
+                cur = p
+            keep = top == 0                           # leaves hanging off the root (drops orphan nodes)
+            newid = np.cumsum(keep) - 1
+            if c_leaf:
+                cl_ = np.concatenate(c_leaf)
+                cn_ = np.concatenate(c_node)
+                cw_ = np.concatenate(c_left)
+                ok = keep[cl_]
+                cl_, cn_, cw_ = newid[cl_[ok]], cn_[ok], cw_[ok]
+            else:
+                cl_ = cn_ = np.zeros(0, dtype=np.int64)
+                cw_ = np.zeros(0, dtype=np.uint8)
+            cf_ = f_[cn_]
+            o = np.lexsort((cn_, cf_, cl_))           # by leaf, then feature, then node (root first)
+            cl_, cn_, cw_, cf_ = cl_[o], cn_[o], cw_[o], cf_[o]
+            nl = int(keep.sum())
+            first = np.ones(cl_.size, dtype=bool)
+            first[1:] = (cl_[1:] != cl_[:-1]) | (cf_[1:] != cf_[:-1])
+            starts = np.nonzero(first)[0]
+            nel.append(np.bincount(cl_[starts], minlength=nl))
+            efeat.append(cf_[starts])
+            ncond.append(np.diff(np.append(starts, cl_.size)))
+            cnode.append(cn_ + base)
+            cleft.append(cw_)
+            kept = leaves[keep]
+            lval.append(np.asarray(t.value, dtype=np.float64)[kept])
+            lcls.append(np.full(nl, self.tclass[ti], dtype=np.int64))
+            tree_leaf_off.append(tree_leaf_off[-1] + nl)
+            base += n
+
+        def cat(parts, dt):
+            return np.concatenate(parts).astype(dt) if parts else np.zeros(0, dtype=dt)
+
+        def offs(counts):
+            return np.concatenate([[0], np.cumsum(cat(counts, np.int64))]).astype(np.int32)
+        ne = cat(nel, np.int64)
+        ef = cat(efeat, np.int32)
+        d = device
+        PT = {"leaf_val": torch.as_tensor(cat(lval, np.float64), device=d),
+              "leaf_cls": torch.as_tensor(cat(lcls, np.int32), device=d),
+              "el_off": torch.as_tensor(offs(nel), device=d),
+              "el_feat": torch.as_tensor(ef, device=d),
+              "cond_off": torch.as_tensor(offs(ncond), device=d),
+              "cond_node": torch.as_tensor(cat(cnode, np.int32), device=d),
+              "cond_left": torch.as_tensor(cat(cleft, np.uint8), device=d),
+              "tree_leaf_off": tree_leaf_off,
+              "L": tree_leaf_off[-1],
+              "max_path": int(ne.max()) if ne.size else 0,
+              "max_feat": int(ef.max()) if ef.size else -1,
+              "max_tree_leaves": int(np.diff(tree_leaf_off).max()) if trees else 0}
+        self._paths = (P, PT)
+        return PT
 
     def predict_range(self, X: torch.Tensor, K: int, start: int, end: int):
         """[N, K] sums of trees [start, end) only (incremental scoring: the

@@ -436,8 +436,12 @@ class H2OXGBoostEstimator(SharedTreeEstimator):
             return torch.stack([1 - mu, mu], 1)
         return mu.view(-1, 1)
 
-    def predict_contributions(self, test_data, **kw):
+    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None,
+                              compare_abs=False, background_frame=None, output_space=False,
+                              output_per_reference=False):
         if getattr(self, "_gblinear", None) is not None:
             raise NotImplementedError("predict_contributions is not available for booster=gblinear (no trees)")
         from .shap import tree_contributions
-        return tree_contributions(self, test_data)
+        return tree_contributions(self, test_data, top_n=top_n, bottom_n=bottom_n, compare_abs=compare_abs,
+                                  background_frame=background_frame, output_space=output_space,
+                                  output_per_reference=output_per_reference)

@@ -900,7 +900,19 @@ def create_app(flow_dir: str | None = None, serve: bool = True) -> FastAPI:
         if p.get("leaf_node_assignment"):
             pr = m.predict_leaf_node_assignment(fr, type=p.get("leaf_node_assignment_type") or "Path")
         elif p.get("predict_contributions"):
-            pr = m.predict_contributions(fr)
+            kw = {}
+            # the schema's defaults (top_n = bottom_n = 0: unsorted output) mean "not given"
+            for k in ("top_n", "bottom_n"):
+                if p.get(k) not in (None, "") and int(float(p[k])) != 0:
+                    kw[k] = int(float(p[k]))
+            for k in ("compare_abs", "output_space", "output_per_reference"):
+                if p.get(k) is True or str(p.get(k)).strip().lower() in ("true", "1"):
+                    kw[k] = True
+            if p.get("background_frame"):
+                bg = p["background_frame"]
+                kw["background_frame"] = _frame(bg.get("name") if isinstance(bg, dict) else bg,
+                                                "background_frame")
+            pr = m.predict_contributions(fr, **kw)
         elif p.get("reconstruction_error"):
             pr = m.anomaly(fr)
         elif p.get("deep_features_hidden_layer") is not None and int(p["deep_features_hidden_layer"]) >= 0:
