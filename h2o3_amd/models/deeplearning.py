@@ -903,6 +903,15 @@ class H2ODeepLearningEstimator(H2OEstimator):
             return H2OFrame.from_vecs([Vec(out[:, j].contiguous(), T_REAL) for j in range(out.shape[1])], names)
         return super().predict(test_data, **kw)
 
+    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None,
+                              compare_abs=False, background_frame=None, output_space=False,
+                              output_per_reference=False):
+        """DeepSHAP against `background_frame` (models/shap_baseline.py,
+        ops/dl_shap_ops.py: the HIP pair kernel on the GPU)."""
+        from .shap_baseline import dl_contributions
+        return dl_contributions(self, test_data, output_format, top_n, bottom_n, compare_abs, background_frame,
+                                output_space, output_per_reference)
+
     def anomaly(self, test_data, per_feature=False):
         X, _ = self._design(test_data)
         with torch.no_grad():

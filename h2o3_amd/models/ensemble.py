@@ -170,5 +170,14 @@ class H2OStackedEnsembleEstimator(H2OEstimator):
         lvl1 = H2OFrame.from_vecs(vecs, names)
         return self._meta._predict_raw(lvl1)
 
+    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None,
+                              compare_abs=False, background_frame=None, output_space=False,
+                              output_per_reference=False):
+        """G-DeepSHAP against `background_frame` through a GLM metalearner
+        (models/shap_baseline.py)."""
+        from .shap_baseline import se_contributions
+        return se_contributions(self, test_data, output_format, top_n, bottom_n, compare_abs, background_frame,
+                                output_space, output_per_reference)
+
     def levelone_frame_id(self):
         return self._output.get("levelone_frame")

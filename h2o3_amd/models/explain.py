@@ -218,12 +218,24 @@ def h_statistic(model, frame: H2OFrame, variables, max_rows=200, seed=0):
 
 
 # ------------------------------------------------------------------ explain()
+def _has_shap(model, background_frame):
+    """Tree models always have a SHAP section; GLM, Deep Learning and Stacked
+    Ensembles have one against a background frame."""
+    if model._spec.nclasses > 2:
+        return False
+    if model.algo in ("gbm", "drf", "xgboost"):
+        return True
+    return background_frame is not None and model.algo in ("glm", "deeplearning", "stackedensemble")
+
+
 def explain(models, frame: H2OFrame, columns=None, top_n_features=5, include_explanations="ALL",
-            exclude_explanations=(), plot=False, **kw):
+            exclude_explanations=(), plot=False, background_frame=None, **kw):
     """h2o.explain(): dict of tables keyed like the reference's explanation
     sections; plot=True adds out["plots"][section] figures (varimp heatmap,
     model correlation, SHAP summary, PD / PD-multi, ICE, residual analysis,
-    learning curve)."""
+    learning curve).  With a background_frame the SHAP section is baseline
+    SHAP against its rows, and also appears for GLM, Deep Learning and Stacked
+    Ensemble models."""
     if not isinstance(models, (list, tuple)):
         models = [models]
     ex = set(exclude_explanations or ())
@@ -255,8 +267,8 @@ def explain(models, frame: H2OFrame, columns=None, top_n_features=5, include_exp
             cols = cols[:top_n_features]
     if "pdp" not in ex:
         out["pdp"] = {c: partial_dependence(m0, frame, c)[0] for c in cols}
-    if "shap_summary" not in ex and m0.algo in ("gbm", "drf", "xgboost") and m0._spec.nclasses <= 2:
-        out["shap_summary"] = m0.predict_contributions(frame).as_data_frame()
+    if "shap_summary" not in ex and _has_shap(m0, background_frame):
+        out["shap_summary"] = m0.predict_contributions(frame, background_frame=background_frame).as_data_frame()
     if "residual_analysis" not in ex and m0._spec.nclasses < 2:
         p = m0.predict(frame).as_data_frame()["predict"].values
         y = frame[m0._spec.y].as_data_frame().iloc[:, 0].values
@@ -284,7 +296,7 @@ def explain(models, frame: H2OFrame, columns=None, top_n_features=5, include_exp
             if "ice" not in ex:
                 figs["ice"] = {c: xp.ice_plot(m0, frame, c) for c in cols}
         if "shap_summary" in out:
-            figs["shap_summary"] = xp.shap_summary_plot(m0, frame)
+            figs["shap_summary"] = xp.shap_summary_plot(m0, frame, background_frame=background_frame)
         if "residual_analysis" in out:
             figs["residual_analysis"] = xp.residual_analysis_plot(m0, frame)
         if "learning_curve" not in ex:
@@ -293,21 +305,23 @@ def explain(models, frame: H2OFrame, columns=None, top_n_features=5, include_exp
     return out
 
 
-def explain_row(models, frame: H2OFrame, row_index, columns=None, top_n_features=5, plot=False, **kw):
+def explain_row(models, frame: H2OFrame, row_index, columns=None, top_n_features=5, plot=False,
+                background_frame=None, **kw):
     if not isinstance(models, (list, tuple)):
         models = [models]
     m0 = models[0]
     row = frame[int(row_index), :]
     out = {}
-    shap = m0.algo in ("gbm", "drf", "xgboost") and m0._spec.nclasses <= 2
+    shap = _has_shap(m0, background_frame)
     if shap:
-        out["shap_explain_row"] = m0.predict_contributions(row).as_data_frame()
+        out["shap_explain_row"] = m0.predict_contributions(row, background_frame=background_frame).as_data_frame()
     cols = columns or list(m0._spec.x)[:top_n_features]
     out["ice"] = {c: partial_dependence(m0, frame, c, row_index=row_index)[0] for c in cols}
     if plot:
         from . import explain_plots as xp
         figs = {"ice": {c: xp.pd_plot(m0, frame, c, row_index=row_index) for c in cols}}
         if shap:
-            figs["shap_explain_row"] = xp.shap_explain_row_plot(m0, frame, row_index)
+            figs["shap_explain_row"] = xp.shap_explain_row_plot(m0, frame, row_index,
+                                                                background_frame=background_frame)
         out["plots"] = figs
     return out

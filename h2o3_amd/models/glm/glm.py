@@ -1769,6 +1769,14 @@ class H2OGeneralizedLinearEstimator(H2OEstimator):
             eta = eta + torch.nan_to_num(frame.vec(off).as_float(torch.float64))
         return eta
 
+    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None,
+                              compare_abs=False, background_frame=None, output_space=False,
+                              output_per_reference=False):
+        """Exact baseline SHAP against `background_frame` (models/shap_baseline.py)."""
+        from ..shap_baseline import glm_contributions
+        return glm_contributions(self, test_data, output_format, top_n, bottom_n, compare_abs, background_frame,
+                                 output_space, output_per_reference)
+
     def coefs_random(self):
         """Random effects per random column and level (HGLM)."""
         return dict(self._output.get("ubeta", {}))

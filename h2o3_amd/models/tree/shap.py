@@ -183,14 +183,30 @@ def _pair_index_vecs(frame, n_local, B, device):
             Vec(torch.arange(B, dtype=torch.float64, device=device).repeat(n_local).contiguous(), T_INT)]
 
 
+def model_background_phi(model, X, Z, output_space=False, output_per_reference=False, max_scratch_bytes=1 << 30):
+    """background_contributions of a trained GBM / XGBoost / DRF model for the
+    score matrices X [F, N] and Z [F, B] (all background rows)."""
+    F = len(model._spec.x)
+    if model.algo == "drf":
+        if model._n_tree_classes() > 1:
+            raise ValueError("Calculating contributions with a background frame is not supported for DRF "
+                             "with binomial_double_trees.")
+        # the forest mean itself: P(class 1) (single-tree binomial) or the prediction
+        ntrees = sum(1 for k in model._forest.tclass if k == 0)
+        return background_contributions(model._forest, X, Z, F, vscale=1.0 / max(1, ntrees),
+                                        output_per_reference=output_per_reference,
+                                        max_scratch_bytes=max_scratch_bytes)
+    return background_contributions(model._forest, X, Z, F, bias=float(model._init_f[0]),
+                                    linkinv=model._dist.linkinv, output_space=output_space,
+                                    output_per_reference=output_per_reference, max_scratch_bytes=max_scratch_bytes)
+
+
 def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=False, background_frame=None,
                        output_space=False, output_per_reference=False):
     """predict_contributions for GBM / XGBoost / DRF (regression + binomial),
     in link space like the reference: row sum == raw margin prediction.
     With a background frame: baseline SHAP against its rows (bias term = mean
     background prediction) instead of path-dependent TreeSHAP."""
-    from ...core.frame import H2OFrame
-    from ...core.vec import Vec, T_REAL, make_enum_from_strings
     spec = model._spec
     if background_frame is None:
         if output_space:
@@ -204,20 +220,10 @@ def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=Fals
     trees = [t for t, k in zip(model._forest.trees, model._forest.tclass) if k == 0]
     extra = []
     if background_frame is not None:
-        if model.algo == "drf" and model._n_tree_classes() > 1:
-            raise ValueError("Calculating contributions with a background frame is not supported for DRF "
-                             "with binomial_double_trees.")
         Z = _gather_background(model._score_matrix(background_frame))
         if Z.shape[1] == 0:
             raise ValueError("background_frame has no rows")
-        if model.algo == "drf":
-            # the forest mean itself: P(class 1) (single-tree binomial) or the prediction
-            phi = background_contributions(model._forest, X, Z, len(names), vscale=1.0 / max(1, len(trees)),
-                                           output_per_reference=output_per_reference)
-        else:
-            phi = background_contributions(model._forest, X, Z, len(names), bias=float(model._init_f[0]),
-                                           linkinv=model._dist.linkinv, output_space=output_space,
-                                           output_per_reference=output_per_reference)
+        phi = model_background_phi(model, X, Z, output_space, output_per_reference)
         if output_per_reference:
             extra = list(zip(_pair_index_vecs(frame, X.shape[1], Z.shape[1], X.device),
                              ["RowIdx", "BackgroundRowIdx"]))
@@ -233,32 +239,5 @@ def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=Fals
     else:
         phi = forest_contributions(trees, X, len(names))
         phi[:, -1] += float(model._init_f[0])
-    if top_n is None and bottom_n is None:
-        vecs = [Vec(phi[:, j].to(torch.float32).contiguous(), T_REAL) for j in range(phi.shape[1])]
-        return H2OFrame.from_vecs(vecs + [v for v, _ in extra], names + ["BiasTerm"] + [n for _, n in extra])
-    # sorted output: top_feature_i / top_value_i (+ bottom_*), BiasTerm last
-    c = phi[:, :-1]
-    key = c.abs() if compare_abs else c
-    order = torch.argsort(key, dim=1, descending=True).cpu().numpy()
-    cn = c.cpu().numpy()
-    cols, out_names = [], []
-    F = c.shape[1]
-    tn = F if top_n is not None and top_n < 0 else (top_n or 0)
-    bn = F if bottom_n is not None and bottom_n < 0 else (bottom_n or 0)
-    import numpy as np
-    for i in range(min(tn, F)):
-        j = order[:, i]
-        cols.append(make_enum_from_strings([names[k] for k in j]))
-        cols.append(Vec(torch.tensor(cn[np.arange(len(j)), j], dtype=torch.float32, device=X.device), T_REAL))
-        out_names += [f"top_feature_{i + 1}", f"top_value_{i + 1}"]
-    for i in range(min(bn, F)):
-        j = order[:, F - 1 - i]
-        cols.append(make_enum_from_strings([names[k] for k in j]))
-        cols.append(Vec(torch.tensor(cn[np.arange(len(j)), j], dtype=torch.float32, device=X.device), T_REAL))
-        out_names += [f"bottom_feature_{i + 1}", f"bottom_value_{i + 1}"]
-    cols.append(Vec(phi[:, -1].to(torch.float32).contiguous(), T_REAL))
-    out_names.append("BiasTerm")
-    for v, n in extra:
-        cols.append(v)
-        out_names.append(n)
-    return H2OFrame.from_vecs(cols, out_names)
+    from ..shap_baseline import contributions_frame
+    return contributions_frame(phi, names, extra, top_n, bottom_n, compare_abs)
