@@ -18,7 +18,11 @@ them.  Here nothing crosses to the host inside a tree:
   every launch grid is a fixed capacity with early-exiting workgroups;
 * so the sequence -- residual, root histogram, per level (child histograms by
   subtraction, split search, ballot partition, next-level segments), leaf
-  gamma sums, leaf values, per-row leaf-value scatter -- is static: one
+  gamma sums, leaf values, per-row leaf values in row order (LeafGather: the
+  stable partition leaves every leaf segment ascending in row id, so the
+  un-permute is a gather over sorted segments, not a scatter; the last level
+  is not compacted, its leaves are read through the go-left flag words of
+  level D-1) -- is static: one
   hipGraph replay per tree on one rank, stream-ordered RCCL collectives
   (histogram reduce-scatter, split-record all-gather, leaf-sum all-reduce)
   between the same kernels on several ranks;
@@ -79,6 +83,12 @@ def _libs():
         lh.h2o_gbm_grad.argtypes = [_cv, _cv, _cv, _ci, _cll, _cv, _cv, _cv]
         lh.h2o_iota_i32.argtypes = [_cv, _cll, _cv]
         lh.h2o_dt_colmask.argtypes = [_ci, _cv, _cv, _cv, _cv, _cv, _ci, _ci, _cv, _cv]
+        lh.h2o_dt_items2.argtypes = [_ci, _cv, _ci, _ci, _ci, _ci, _ci, _cv, _cv, _cv, _cv, _cv]
+        lh.h2o_leaf_flag_sums_dev.argtypes = [_cv, _cv, _cv, _ci, _cv, _cv, _ci, _ci, _cv, _cv, _cv]
+        lh.h2o_leaf_gather_lds.argtypes = [_ci, _ci]
+        lh.h2o_leaf_gather_items.argtypes = [_cll, _ci]
+        lh.h2o_leaf_gather_dev.argtypes = [_cv, _ci, _ci, _ci, _cv, _cv, _cv, _cv, _cll, _ci, _ci, _cv, _cv, _cv, _cv,
+                                           _cv, _cv]
         lh._typed_dt = True
     if not getattr(ls, "_typed_dt", False):
         ls.h2o_split_find_b.argtypes = [_cv, _ci, _ci, _ci, _cv, _cv, _cv] + [_cd] * 5 + [_ci, _cv, _cv, _ci, _cv]
@@ -123,6 +133,40 @@ def supported(drv) -> str | None:
     if not drv.grower.pos_payload_ok():
         return "payload path"
     return None
+
+
+def gather_rows(n):
+    """Rows per workgroup of the leaf gather (LDS: 4 bytes per row).  8192 up
+    to 100M rows (12.5M rows: 1526 workgroups; sweep in profiles/README.md);
+    H2O3_LEAF_GATHER_R overrides (a power of two >= 256)."""
+    ev = tree_ops.env("H2O3_LEAF_GATHER_R")
+    return int(ev) if ev else 8192
+
+
+class LeafGather:
+    """Buffers + launch of the leaf gather (tree_hist.hip lg_*_kernel): per-row
+    leaf values in row order from the tree record and the final `ridx`, whose
+    leaf segments are ascending in row id (ridx = iota at the root, stable
+    partition).  Writes what h2o_leaf_scatter_dev writes, bit for bit."""
+
+    def __init__(self, lh, N, D, dev, R=None):
+        self.lh, self.N, self.D = lh, int(N), int(D)
+        self.nh = (1 << (D + 1)) - 1
+        self.R = int(R) if R else gather_rows(N)
+        self.scap = 1 << D
+        nb = -(-self.N // self.R)
+        self.segs = torch.zeros(self.scap * 4, dtype=torch.int32, device=dev)
+        self.items = torch.zeros(2 * lh.h2o_leaf_gather_items(self.N, self.scap), dtype=torch.int32, device=dev)
+        self.nseg = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.T = torch.zeros((nb + 1) * self.scap, dtype=torch.int32, device=dev)
+
+    def run(self, rec, ridx, vals, dbuf, flags=None, slot_wb=None):
+        """`flags` / `slot_wb` given: the last level was not compacted (`ridx`
+        is in level-(D-1) order; slot_wb = h2o_dt_items2's per-slot flag base)."""
+        last = 0 if slot_wb is None else 1
+        _ck(self.lh.h2o_leaf_gather_dev(_ptr(rec), self.nh, self.D, last, _ptr(slot_wb), _ptr(ridx), _ptr(flags),
+                                        _ptr(vals), self.N, self.R, self.scap, _ptr(self.segs), _ptr(self.items),
+                                        _ptr(self.nseg), _ptr(self.T), _ptr(dbuf), _stream()), "leaf_gather_dev")
 
 
 class DevTreeGBM:
@@ -216,6 +260,14 @@ class DevTreeGBM:
             self.cs_m = torch.zeros(1, dtype=torch.int32, device=dev)
             self.cs_k = torch.zeros(max(D, 1), dtype=torch.int32, device=dev)
             self.cs_seed = torch.zeros(max(D, 1), dtype=torch.int64, device=dev)
+        # per-row leaf values: gather over the sorted leaf segments
+        # (H2O3_LEAF_GATHER=0: the random-store scatter), and no compaction of
+        # the last level (H2O3_DEV_LAST_LEVEL=0 restores it; needs the gather:
+        # the scatter has no flag-aware read)
+        self.gather = os.environ.get("H2O3_LEAF_GATHER", "1") != "0" and N > 0
+        self.last_level = self.gather and os.environ.get("H2O3_DEV_LAST_LEVEL", "1") != "0"
+        self.lg = LeafGather(self.lh, N, D, dev) if self.gather else None
+        self.slot_wb = torch.zeros(n_lvl_max, dtype=i32, device=dev)
         self.graph = None
         self._hv = [None, None]
         self._k = 0
@@ -368,13 +420,23 @@ class DevTreeGBM:
         if self.W > 1:
             self._merge(recl, n)
         s = _stream()
-        _ck(lh.h2o_dt_items(0, _ptr(recl), n, self.D, 0, self.chunk_p, self.cap_p, _ptr(self.pwork), _ptr(self.fbase),
-                            _ptr(self.counts), s), "dt_items(part)")
+        skip = self.last_level and d == self.D - 1
+        _ck(lh.h2o_dt_items2(0, _ptr(recl), n, self.D, 0, self.chunk_p, self.cap_p, _ptr(self.pwork),
+                             _ptr(self.fbase), _ptr(self.slot_wb) if skip else None, _ptr(self.counts), s),
+            "dt_items(part)")
         _ck(lh.h2o_part_flags_dev(_ptr(self.pcodes), 1, self.prs, self.pfs, _ptr(self.ridx[cur]), _ptr(self.pwork),
                                   _ptr(self.fbase), self.cap_p, _ptr(self.feat_i), _ptr(self.mask), Bs,
                                   _ptr(self.flags), _ptr(self.cnt), _ptr(self.counts), s), "part_flags_dev")
         _ck(lh.h2o_dt_offsets(_ptr(self.cnt), _ptr(self.pwork), _ptr(self.counts), _ptr(recl), n,
                               _ptr(self._rec_lvl(d + 1)), _ptr(self.loff), _ptr(self.roff), s), "dt_offsets")
+        if skip:
+            # last level: nothing builds a histogram from its segments, so the
+            # rows stay in level-(D-1) order; the children's leaf sums come from
+            # this level's payload and the flag words just written
+            _ck(lh.h2o_leaf_flag_sums_dev(_ptr(self.pos[cur]), _ptr(self.pwork), _ptr(self.fbase), self.cap_p,
+                                          _ptr(self.flags), _ptr(recl), self.D, 1 if self.bern else 0,
+                                          _ptr(self.sums), _ptr(self.counts), s), "leaf_flag_sums_dev")
+            return cur
         nxt = cur ^ 1
         _ck(lh.h2o_part_compact_dev(_ptr(self.ridx[cur]), _ptr(self.pwork), _ptr(self.fbase), self.cap_p,
                                     _ptr(self.flags), _ptr(self.loff), _ptr(self.roff), _ptr(self.ridx[nxt]),
@@ -383,7 +445,7 @@ class DevTreeGBM:
         return nxt
 
     def _sequence(self):
-        """One tree: residual -> levels -> leaf values -> per-row scatter."""
+        """One tree: residual -> levels -> leaf values -> per-row leaf values."""
         lh, drv = self.lh, self.drv
         s = _stream()
         y = drv.yb if self.bern else torch.nan_to_num(drv.yf)
@@ -400,8 +462,8 @@ class DevTreeGBM:
         for d in range(self.D):
             cur = self._level(d, cur)
         s = _stream()
-        _ck(lh.h2o_dt_items(2, _ptr(self.rec), self.nh, self.D, 0, self.chunk_l, self.cap_l, _ptr(self.lwork), None,
-                            _ptr(self.counts), s), "dt_items(leaf)")
+        _ck(lh.h2o_dt_items(3 if self.last_level else 2, _ptr(self.rec), self.nh, self.D, 0, self.chunk_l, self.cap_l,
+                            _ptr(self.lwork), None, _ptr(self.counts), s), "dt_items(leaf)")
         _ck(lh.h2o_leaf_pos_dev(_ptr(self.pos[cur]), _ptr(self.lwork), self.cap_l, 1 if self.bern else 0,
                                 _ptr(self.sums), _ptr(self.counts), s), "leaf_pos_dev")
         if self.W > 1:
@@ -409,8 +471,12 @@ class DevTreeGBM:
         s = _stream()
         _ck(lh.h2o_dt_leaf_vals(_ptr(self.rec), _ptr(self.sums), self.nh, self.D, _ptr(self.lr_t), self.maxabs,
                                 _ptr(self.vals), s), "dt_leaf_vals")
-        _ck(lh.h2o_leaf_scatter_dev(_ptr(self.ridx[cur]), _ptr(self.lwork), self.cap_l, _ptr(self.vals),
-                                    _ptr(self.dbuf), _ptr(self.counts), s), "leaf_scatter_dev")
+        if self.gather:
+            self.lg.run(self.rec, self.ridx[cur], self.vals, self.dbuf, self.flags if self.last_level else None,
+                        self.slot_wb if self.last_level else None)
+        else:
+            _ck(lh.h2o_leaf_scatter_dev(_ptr(self.ridx[cur]), _ptr(self.lwork), self.cap_l, _ptr(self.vals),
+                                        _ptr(self.dbuf), _ptr(self.counts), s), "leaf_scatter_dev")
         self.cur = cur
 
     def set_col_sampling(self, tree_mask):

@@ -2057,7 +2057,10 @@ enum {
 //   kind 1 (child): the lighter child of a splitting parent slot (by the
 //                   weight channel wch of the record's L / R sums; ties left);
 //   kind 2 (leaf) : heap node i when it is a leaf (count > 0 and level == D or
-//                   no split); i is a heap index into the whole record.
+//                   no split); i is a heap index into the whole record;
+//   kind 3 (early leaf): kind 2 restricted to levels < D -- the last level is
+//                   not compacted (its leaves are read through the flag words
+//                   of level D-1, leaf_flag_sums_kernel / lg_gather_kernel).
 __device__ __forceinline__ void dt_seg(int kind, const double* __restrict__ rec, int i, int D, int wch,
                                        long long& start, long long& cnt) {
   const double* r = rec + (size_t)i * DT_RS;
@@ -2075,18 +2078,20 @@ __device__ __forceinline__ void dt_seg(int kind, const double* __restrict__ rec,
     }
   } else {
     const int lv = 31 - __clz(i + 1);
-    if (ct > 0 && (lv == D || !(r[DT_OK] > 0.0))) { start = st; cnt = ct; }
+    if (ct > 0 && ((lv == D && kind == 2) || (lv < D && !(r[DT_OK] > 0.0)))) { start = st; cnt = ct; }
   }
 }
 
 // One workgroup: per-slot chunk counts scanned into item bases (LDS), then all
 // threads write the items (slot found by binary search over the bases).
 // work[it] = (slot, start, count, k); fbase[it] (optional) = the item's first
-// ballot word (partition flags: the slot's words are contiguous, chunk % 64 == 0).
+// ballot word (partition flags: the slot's words are contiguous, chunk % 64 == 0);
+// slot_wb[i] (optional) = slot i's first ballot word.
 // counts[1] = #items (<= cap).
 __global__ __launch_bounds__(1024) void dt_items_kernel(int kind, const double* __restrict__ rec, int n, int D,
                                                         int wch, int chunk, int cap, int4* __restrict__ work,
-                                                        int* __restrict__ fbase, int* __restrict__ counts) {
+                                                        int* __restrict__ fbase, int* __restrict__ slot_wb,
+                                                        int* __restrict__ counts) {
   __shared__ int sb[DT_MAXN + 1];
   __shared__ int wb[DT_MAXN + 1];
   __shared__ long long wtot[2][16];
@@ -2127,6 +2132,8 @@ __global__ __launch_bounds__(1024) void dt_items_kernel(int kind, const double* 
     __syncthreads();
   }
   const int total = (int)min(carry[0], (long long)cap);
+  if (slot_wb != nullptr)
+    for (int i = threadIdx.x; i < n; i += blockDim.x) slot_wb[i] = wb[i];
   for (int it = threadIdx.x; it < total; it += blockDim.x) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {                       // last slot whose base is <= it (empty slots precede it)
@@ -2280,14 +2287,291 @@ __global__ void dt_root_kernel(double* __restrict__ rec, long long N) {
   if (threadIdx.x == 0) { rec[DT_ST] = 0.0; rec[DT_CT] = (double)N; }
 }
 
+// Leaf sums of the level-D leaves WITHOUT compacting the last level: the
+// level-(D-1) payload is streamed in its own order and every row goes to the
+// left / right child of its slot by its go-left flag bit (part_flags_kernel's
+// words).  work / fbase = the level's partition items; slots that do not split
+// are leaves of level D-1 and belong to leaf_pos_kernel (kind 3).  Channels
+// as leaf_pos_kernel; sums[2 * child + {0, 1}], child = 2 * heap + 1 (left)
+// or + 2 (right), one f64 gbl_add per workgroup and channel.
+__global__ __launch_bounds__(256) void leaf_flag_sums_kernel(
+    const float* __restrict__ zp, const int4* __restrict__ work, const int* __restrict__ fbase,
+    const unsigned long long* __restrict__ flags, const double* __restrict__ rec_lvl, int heap0, int mode,
+    double* __restrict__ out, const int* __restrict__ nw_dev) {
+  if (nw_dev != nullptr && (int)blockIdx.x >= nw_dev[1]) return;
+  const int4 wk = work[blockIdx.x];
+  if (!(rec_lvl[(size_t)wk.x * DT_RS + DT_OK] > 0.0)) return;
+  const int fb = fbase[blockIdx.x];
+  const int end = wk.y + wk.z;
+  double la = 0.0, lb = 0.0, ra = 0.0, rb = 0.0;
+  constexpr int U = 4;   // loads of U strides in flight per thread (one per iteration ran at 1.8 TB/s)
+  for (int base = wk.y + (int)threadIdx.x; base < end; base += 256 * U) {
+    float z[U];
+    unsigned long long w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int pc = min(base + u * 256, end - 1);
+      z[u] = zp[pc];
+      w[u] = flags[fb + ((pc - wk.y) >> 6)];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int p = base + u * 256;
+      const bool L = (w[u] >> ((p - wk.y) & 63)) & 1ull;
+      if (p < end && z[u] == z[u]) {
+        const double az = fabs((double)z[u]);
+        const double b = mode == 1 ? az * (1.0 - az) : 1.0;
+        if (L) { la += (double)z[u]; lb += b; } else { ra += (double)z[u]; rb += b; }
+      }
+    }
+  }
+  la = wave_sum(la); lb = wave_sum(lb); ra = wave_sum(ra); rb = wave_sum(rb);
+  __shared__ double red[4][4];
+  if (lane_id() == 0) { red[0][wave_id()] = la; red[1][wave_id()] = lb; red[2][wave_id()] = ra; red[3][wave_id()] = rb; }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int c = threadIdx.x;
+    double* o = out + 2 * (size_t)(2 * (heap0 + wk.x) + 1 + (c >> 1)) + (c & 1);
+    gbl_add(o, red[c][0] + red[c][1] + red[c][2] + red[c][3]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Leaf gather: the per-row leaf value in ROW order without a scatter.  Every
+// tree starts from ridx = iota and the partition is stable, so at the end of
+// a tree ridx is a permutation of the rows cut into segments, each ascending
+// in row id.  Rows are cut into blocks of R; the slice of segment s that
+// falls into block b is [T[b][s], T[b+1][s]) (lg_bounds_kernel, one streaming
+// pass over ridx); a workgroup reads its slices as contiguous runs, places
+// the values in LDS at ridx[p] - b * R and writes its R rows of d with
+// 16-byte stores.  d is bit for bit what leaf_scatter_kernel writes
+// (vals[leaf] copied per row).
+//
+// Dispatch: no rule on (N, segments).  With evenly filled leaves the gather
+// beats or ties the scatter at every measured shape (100M rows: 0.50 against
+// 1.72 ms at 256 leaves, 0.99-1.18 against 1.90 ms at 2048; 12.5M rows:
+// 0.078 against 0.123 ms and 0.135-0.151 against 0.155 ms).  It loses only
+// when one leaf holds most of the rows (90 %: by 0.03 ms at 12.5M x 256, by
+// 0.5 ms at 100M x 2048), which the host does not know; H2O3_LEAF_GATHER=0
+// (devtree.py) restores the scatter.  Numbers: profiles/README.md.
+//
+// segs[s] = (heap, start, count, fb): fb < 0 -- a leaf, every row takes
+// vals[heap]; fb >= 0 -- a splitting node of level D-1 whose rows were NOT
+// compacted: row at position p takes the left (2 heap + 1) or right
+// (2 heap + 2) child's value by bit (p - start) % 64 of flags[fb + (p - start) / 64].
+// ---------------------------------------------------------------------------
+#define LG_MAXSEG 2048
+__global__ __launch_bounds__(1024) void lg_segs_kernel(const double* __restrict__ rec, int nh, int D, int last,
+                                                       const int* __restrict__ slot_wb, int cap, long long N,
+                                                       int chk, int icap, int4* __restrict__ segs,
+                                                       int2* __restrict__ items, int* __restrict__ nseg) {
+  __shared__ int wcnt[16];
+  __shared__ int carry;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
+  const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nh; base += blockDim.x) {
+    const int i = base + threadIdx.x;
+    bool is = false;
+    int4 sg = make_int4(0, 0, 0, -1);
+    if (i < nh) {
+      const double* r = rec + (size_t)i * DT_RS;
+      const int lv = 31 - __clz(i + 1);
+      // clamped to the row range: the searches and runs below index ridx by these
+      const long long st = min(max((long long)r[DT_ST], 0ll), N);
+      const long long ct = min((long long)r[DT_CT], N - st);
+      const bool ok = r[DT_OK] > 0.0;
+      if (ct > 0) {
+        if (last == 0) {
+          is = lv == D || !ok;
+        } else if (lv < D) {
+          is = !ok || lv == D - 1;
+          if (ok && lv == D - 1) sg.w = slot_wb[i - ((1 << (D - 1)) - 1)];
+        }
+      }
+      sg.x = i; sg.y = (int)st; sg.z = (int)ct;
+    }
+    const unsigned long long bal = __ballot(is);
+    if (lane == 0) wcnt[wv] = __popcll(bal);
+    __syncthreads();
+    int pre = carry, tot = 0;
+    for (int w = 0; w < nwv; ++w) { pre += (w < wv) ? wcnt[w] : 0; tot += wcnt[w]; }
+    const int pos = pre + __popcll(bal & below);
+    if (is && pos < cap) segs[pos] = sg;
+    __syncthreads();
+    if (threadIdx.x == 0) carry += tot;
+    __syncthreads();
+  }
+  const int S = min(carry, cap);
+  // work items of the bounds pass: (segment, k) = positions [k * chk, (k + 1) * chk) of the segment
+  __shared__ int ib[LG_MAXSEG + 1];
+  __shared__ int icarry;
+  if (threadIdx.x == 0) icarry = 0;
+  __syncthreads();   // also publishes segs[] to the whole workgroup
+  for (int base = 0; base < S; base += blockDim.x) {
+    const int s = base + threadIdx.x;
+    const int nch = s < S ? (segs[s].z + chk - 1) / chk : 0;
+    int x = nch;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(x, o, 64);
+      if (lane >= o) x += t;
+    }
+    if (lane == 63) wcnt[wv] = x;
+    __syncthreads();
+    int off = icarry, tot = 0;
+    for (int w = 0; w < nwv; ++w) { off += (w < wv) ? wcnt[w] : 0; tot += wcnt[w]; }
+    if (s < S) ib[s] = off + x - nch;
+    __syncthreads();
+    if (threadIdx.x == 0) icarry += tot;
+    __syncthreads();
+  }
+  const int nit = min(icarry, icap);
+  for (int it = threadIdx.x; it < nit; it += blockDim.x) {
+    int a = 0, b = S - 1;
+    while (a < b) {                         // last segment whose first item is <= it (every segment has >= 1)
+      const int mid = (a + b + 1) >> 1;
+      if (ib[mid] <= it) a = mid; else b = mid - 1;
+    }
+    items[it] = make_int2(a, it - ib[a]);
+  }
+  if (threadIdx.x == 0) { nseg[0] = S; nseg[1] = nit; }
+}
+
+// T[b * scap + s] = first position of segment s whose row id is >= b * R
+// (b = 0 .. nb; b = nb gives the segment's end), R = 1 << sh.  One streaming
+// pass over ridx instead of a binary search per entry (at 2048 segments the
+// searches cost more than the scatter they replace): position p writes the
+// entries of the blocks that begin between its left neighbour's row and its
+// own, the segment's last position those of the blocks after it, so every
+// entry is written exactly once.
+__global__ __launch_bounds__(256) void lg_bounds_kernel(const int* __restrict__ ridx, const int4* __restrict__ segs,
+                                                        const int* __restrict__ nseg, const int2* __restrict__ items,
+                                                        int sh, int nb, int scap, int chk, int* __restrict__ T) {
+  if ((int)blockIdx.x >= nseg[1]) return;
+  const int2 it = items[blockIdx.x];
+  const int s = it.x;
+  const int4 sg = segs[s];
+  const int send = sg.y + sg.z;
+  const int beg = sg.y + it.y * chk, end = min(send, beg + chk);
+  for (int p = beg + (int)threadIdx.x; p < end; p += 256) {
+    const int bcur = min(ridx[p] >> sh, nb - 1);
+    const int bprev = p > sg.y ? (ridx[p - 1] >> sh) : -1;
+    for (int b = max(bprev + 1, 0); b <= bcur; ++b) T[(size_t)b * scap + s] = p;
+    if (p == send - 1)
+      for (int b = max(bcur + 1, 0); b <= nb; ++b) T[(size_t)b * scap + s] = send;
+  }
+}
+
+#define LG_NONE 0xFFFFFFFFu   // LDS slot no segment wrote (a row outside every leaf keeps its d)
+__global__ __launch_bounds__(1024) void lg_gather_kernel(const int* __restrict__ ridx, const int4* __restrict__ segs,
+                                                        const int* __restrict__ nseg, const int* __restrict__ T,
+                                                        int scap, const unsigned long long* __restrict__ flags,
+                                                        const float* __restrict__ vals, long long N, int R,
+                                                        float* __restrict__ d) {
+  extern __shared__ __attribute__((aligned(16))) int lg_lds[];   // v[] is read back as uint4
+  unsigned int* v = reinterpret_cast<unsigned int*>(lg_lds);   // [R] value bits by local row
+  int* pre = lg_lds + R;                                        // [scap + 1] first flat index of each slice
+  int* lo = pre + scap + 1;                                     // [scap] first position of each slice
+  __shared__ int wtot[16];
+  const int nt = blockDim.x, nwv = nt >> 6;   // LDS per wave stays ~4 KB: nt follows R (h2o_leaf_gather_dev)
+  const int S = nseg[0];
+  const long long row0 = (long long)blockIdx.x * R;
+  const int nrows = (int)min((long long)R, N - row0);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < R; i += nt) v[i] = LG_NONE;
+  // slice lengths, exclusive scan over the segments (K consecutive per thread)
+  const int K = (S + nt - 1) / nt;
+  const int s0 = threadIdx.x * K;
+  const int* Ta = T + (size_t)blockIdx.x * scap;
+  const int* Tb = Ta + scap;
+  int sum = 0;
+  for (int k = 0; k < K; ++k) {
+    const int s = s0 + k;
+    if (s < S) {
+      const int a = Ta[s];
+      lo[s] = a;
+      pre[s] = sum;
+      sum += max(Tb[s] - a, 0);
+    }
+  }
+  int x = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(x, o, 64);
+    if (lane >= o) x += t;
+  }
+  if (lane == 63) wtot[wv] = x;
+  __syncthreads();
+  int off = x - sum;
+  int total = 0;
+  for (int w = 0; w < nwv; ++w) { off += (w < wv) ? wtot[w] : 0; total += wtot[w]; }
+  for (int k = 0; k < K; ++k) {
+    const int s = s0 + k;
+    if (s < S) pre[s] += off;
+  }
+  if (threadIdx.x == 0) pre[S] = total;
+  __syncthreads();
+  // flat index j -> (slice, position): consecutive threads read consecutive
+  // positions of a slice; a long slice is shared by all threads, a short one
+  // costs only its own entries
+  constexpr int U = 4;
+  for (int j0 = threadIdx.x; j0 < total; j0 += nt * U) {
+    int sl[U], p[U], r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = min(j0 + u * nt, total - 1);
+      int a = 0, b = S - 1;
+      while (a < b) {                      // first slice whose end is past j
+        const int mid = (a + b) >> 1;
+        if (pre[mid + 1] > j) b = mid; else a = mid + 1;
+      }
+      sl[u] = a;
+      p[u] = lo[a] + (j - pre[a]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) r[u] = ridx[p[u]];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int4 sg = segs[sl[u]];
+      int h = sg.x;
+      if (sg.w >= 0) {
+        const int q = p[u] - sg.y;
+        h = 2 * h + (((flags[sg.w + (q >> 6)] >> (q & 63)) & 1ull) ? 1 : 2);
+      }
+      const long long li = (long long)r[u] - row0;
+      if (j0 + u * nt < total && li >= 0 && li < nrows) v[li] = __float_as_uint(vals[h]);
+    }
+  }
+  __syncthreads();
+  float* dr = d + row0;
+  for (int i = threadIdx.x * 4; i < nrows; i += nt * 4) {
+    const uint4 q = *reinterpret_cast<const uint4*>(v + i);
+    if (i + 3 < nrows && q.x != LG_NONE && q.y != LG_NONE && q.z != LG_NONE && q.w != LG_NONE) {
+      *reinterpret_cast<uint4*>(dr + i) = q;
+    } else {
+      const unsigned int e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (i + k < nrows && e[k] != LG_NONE) dr[i + k] = __uint_as_float(e[k]);
+    }
+  }
+}
+
 extern "C" {
+
+int h2o_dt_items2(int kind, const double* rec, int n, int D, int wch, int chunk, int cap, int* work, int* fbase,
+                  int* slot_wb, int* counts, hipStream_t s) {
+  if (n <= 0 || n > DT_MAXN || chunk <= 0 || (fbase != nullptr && chunk % 64 != 0)) return -1;
+  hipLaunchKernelGGL(dt_items_kernel, dim3(1), dim3(1024), 0, s, kind, rec, n, D, wch, chunk, cap, (int4*)work, fbase,
+                     slot_wb, counts);
+  return (int)hipGetLastError();
+}
 
 int h2o_dt_items(int kind, const double* rec, int n, int D, int wch, int chunk, int cap, int* work, int* fbase,
                  int* counts, hipStream_t s) {
-  if (n <= 0 || n > DT_MAXN || chunk <= 0 || (fbase != nullptr && chunk % 64 != 0)) return -1;
-  hipLaunchKernelGGL(dt_items_kernel, dim3(1), dim3(1024), 0, s, kind, rec, n, D, wch, chunk, cap, (int4*)work, fbase,
-                     counts);
-  return (int)hipGetLastError();
+  return h2o_dt_items2(kind, rec, n, D, wch, chunk, cap, work, fbase, nullptr, counts, s);
 }
 
 int h2o_dt_offsets(const int* cnt, const int* work, const int* counts, double* rec, int n, double* rec_next, int* loff,
@@ -2353,6 +2637,56 @@ int h2o_leaf_scatter_dev(const int* ridx, const int* work, int n_cap, const floa
                          hipStream_t s) {
   if (n_cap <= 0) return 0;
   hipLaunchKernelGGL(leaf_scatter_kernel, dim3(n_cap), dim3(256), 0, s, ridx, (const int4*)work, val, d, counts);
+  return (int)hipGetLastError();
+}
+
+// Last-level leaf sums from the level-(D-1) order (rec_lvl = that level's
+// records, work / fbase / counts = its partition items).
+int h2o_leaf_flag_sums_dev(const float* zp, const int* work, const int* fbase, int n_cap,
+                           const unsigned long long* flags, const double* rec_lvl, int D, int mode, double* out,
+                           const int* counts, hipStream_t s) {
+  if (n_cap <= 0) return 0;
+  if (D < 1) return -1;
+  hipLaunchKernelGGL(leaf_flag_sums_kernel, dim3(n_cap), dim3(256), 0, s, zp, (const int4*)work, fbase, flags, rec_lvl,
+                     (1 << (D - 1)) - 1, mode, out, counts);
+  return (int)hipGetLastError();
+}
+
+// Leaf gather (see lg_gather_kernel).  scap = segment capacity (>= 2^D leaves),
+// R = rows per block (a power of two >= 256), T = [(N + R - 1) / R + 1][scap]
+// int32, segs = [scap] int4, items = [h2o_leaf_gather_items(N, scap)] int2,
+// nseg = 2 ints.  last != 0: level D was not compacted (slot_wb = the
+// flag-word bases of the level-(D-1) slots, from h2o_dt_items2).
+#define LG_CHK 8192   // positions per work item of the bounds pass
+int h2o_leaf_gather_lds(int R, int scap) { return (R + 2 * scap + 1) * (int)sizeof(int); }
+int h2o_leaf_gather_items(long long N, int scap) { return (int)(scap + N / LG_CHK + 1); }
+
+int h2o_leaf_gather_dev(const double* rec, int nh, int D, int last, const int* slot_wb, const int* ridx,
+                        const unsigned long long* flags, const float* vals, long long N, int R, int scap, int* segs,
+                        int* items, int* nseg, int* T, float* d, hipStream_t s) {
+  if (N <= 0) return 0;
+  if (nh <= 0 || D < 1 || R < 256 || (R & (R - 1)) != 0 || scap < (1 << D) || scap > LG_MAXSEG ||
+      N > (1ll << 31) - (1 << 24))
+    return -1;
+  if (last != 0 && (slot_wb == nullptr || flags == nullptr)) return -1;
+  const int lds = h2o_leaf_gather_lds(R, scap);
+  if (lds > 160 * 1024 - 256) return -1;
+  static int lds_set = 0;
+  if (lds > lds_set) {   // first call is outside any capture (devtree runs its first tree eagerly)
+    if (hipFuncSetAttribute((const void*)lg_gather_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
+        hipSuccess)
+      return -2;
+    lds_set = lds;
+  }
+  const int nb = (int)((N + R - 1) / R);
+  const int icap = h2o_leaf_gather_items(N, scap);
+  const int nt = min(1024, max(256, R / 16));
+  hipLaunchKernelGGL(lg_segs_kernel, dim3(1), dim3(1024), 0, s, rec, nh, D, last, slot_wb, scap, N, LG_CHK, icap,
+                     (int4*)segs, (int2*)items, nseg);
+  hipLaunchKernelGGL(lg_bounds_kernel, dim3(icap), dim3(256), 0, s, ridx, (const int4*)segs, nseg,
+                     (const int2*)items, 31 - __builtin_clz(R), nb, scap, LG_CHK, T);
+  hipLaunchKernelGGL(lg_gather_kernel, dim3(nb), dim3(nt), lds, s, ridx, (const int4*)segs, nseg, T, scap, flags,
+                     vals, N, R, d);
   return (int)hipGetLastError();
 }
 
