@@ -82,6 +82,7 @@ def _libs():
                                    _ci, _cll, _ci, _cv, _cv, _cv, _cv]
         lh.h2o_gbm_grad.argtypes = [_cv, _cv, _cv, _ci, _cll, _cv, _cv, _cv]
         lh.h2o_iota_i32.argtypes = [_cv, _cll, _cv]
+        lh.h2o_dt_root_leaf_iota.argtypes = [_cv, _cv, _cll, _cv]
         lh.h2o_dt_colmask.argtypes = [_ci, _cv, _cv, _cv, _cv, _cv, _ci, _ci, _cv, _cv]
         lh.h2o_dt_items2.argtypes = [_ci, _cv, _ci, _ci, _ci, _ci, _ci, _cv, _cv, _cv, _cv, _cv]
         lh.h2o_leaf_flag_sums_dev.argtypes = [_cv, _cv, _cv, _ci, _cv, _cv, _ci, _ci, _cv, _cv, _cv]
@@ -192,8 +193,19 @@ class DevTreeGBM:
         # histogram layout and fixed-point scales (static: the chunk sizes follow
         # from N exactly as the level loop's do for a full frontier)
         self.pack = tree_ops.env("H2O3_HIST_PACK", "1") == "1"
+        # lane mapping of a ragged last feature group: read here, before the graph is captured
+        self.ragged = tree_ops.bm_ragged()
+        # a tree starts from ridx = iota: with max_depth >= 2 level 0 is always
+        # compacted, so the root kernels take "row id = position" (a null
+        # ridx) and nothing writes or reads the 4 N bytes of iota
+        # (H2O3_DEV_ROOT_IDENT=0 restores them).  max_depth == 1: the per-row
+        # leaf values are read through ridx[0], which stays iota.  The
+        # histogram kernel has id-free instances for the packed G = 64 layout
+        # with 8 codes per lane (the default).
         n_fg, G = tree_ops.bm_groups(bd.F, bd.Fp, Bs, self.pack)
         self.n_fg, self.G = n_fg, G
+        self.root_ident = D >= 2 and tree_ops.env("H2O3_DEV_ROOT_IDENT", "1") != "0" and self.pack and G == 64 \
+            and tree_ops.env("H2O3_HIST_BM_LW", "2") != "1"
         self.chunk_r = tree_ops.hist_chunk(N, n_fg)
         self.chunk_c = tree_ops.hist_chunk((N + 1) // 2, n_fg)
         if self.pack and max(self.chunk_r, self.chunk_c) >= (1 << 23):
@@ -337,6 +349,10 @@ class DevTreeGBM:
         off = (1 << d) - 1
         return self.rec[off * RS:]
 
+    def _ridx_ptr(self, d, cur):
+        """Row ids of level d's kernels: null at an id-free root (row id = position)."""
+        return None if (d == 0 and self.root_ident) else _ptr(self.ridx[cur])
+
     def _hist(self, d, cur):
         """Level d's histogram [Fl, 2^d, Bs, C] (+ w*y*y [2^d]) into buffer d % 2."""
         lh = self.lh
@@ -351,7 +367,8 @@ class DevTreeGBM:
             nh = bd.F * Bs * C
             buf = self.Hroot
             buf.zero_()
-            _ck(lh.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(self.ridx[cur]), _ptr(self.pos[cur]), None,
+            tree_ops.set_bm_ragged(lh, self.ragged)
+            _ck(lh.h2o_hist_bm(_ptr(bd.codes), bd.Fp, self._ridx_ptr(0, cur), _ptr(self.pos[cur]), None,
                                _ptr(self.hwork), self.cap_r, bd.F, 0, Bs, self.s_r[0], self.s_r[1], _ptr(buf), 1, 0,
                                _ptr(buf[nh:]), 1, self.bq_r, self.G, None, _ptr(self.counts), _ptr(self.part), s),
                 "hist_bm(root)")
@@ -368,6 +385,7 @@ class DevTreeGBM:
         nhb = bd.F * npar * Bs * C
         buf = self.Hb[:nhb + npar]
         buf.zero_()
+        tree_ops.set_bm_ragged(lh, self.ragged)
         _ck(lh.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(self.ridx[cur]), _ptr(self.pos[cur]), None, _ptr(self.hwork),
                            self.cap_c, bd.F, 0, Bs, self.s_c[0], self.s_c[1], _ptr(buf), npar, 0, _ptr(buf[nhb:]), 1,
                            self.bq_c, self.G, None, _ptr(self.counts), _ptr(self.part), s), "hist_bm(child)")
@@ -424,9 +442,9 @@ class DevTreeGBM:
         _ck(lh.h2o_dt_items2(0, _ptr(recl), n, self.D, 0, self.chunk_p, self.cap_p, _ptr(self.pwork),
                              _ptr(self.fbase), _ptr(self.slot_wb) if skip else None, _ptr(self.counts), s),
             "dt_items(part)")
-        _ck(lh.h2o_part_flags_dev(_ptr(self.pcodes), 1, self.prs, self.pfs, _ptr(self.ridx[cur]), _ptr(self.pwork),
-                                  _ptr(self.fbase), self.cap_p, _ptr(self.feat_i), _ptr(self.mask), Bs,
-                                  _ptr(self.flags), _ptr(self.cnt), _ptr(self.counts), s), "part_flags_dev")
+        _ck(lh.h2o_part_flags_dev(_ptr(self.pcodes), 1, self.prs, self.pfs, self._ridx_ptr(d, cur),
+                                  _ptr(self.pwork), _ptr(self.fbase), self.cap_p, _ptr(self.feat_i), _ptr(self.mask),
+                                  Bs, _ptr(self.flags), _ptr(self.cnt), _ptr(self.counts), s), "part_flags_dev")
         _ck(lh.h2o_dt_offsets(_ptr(self.cnt), _ptr(self.pwork), _ptr(self.counts), _ptr(recl), n,
                               _ptr(self._rec_lvl(d + 1)), _ptr(self.loff), _ptr(self.roff), s), "dt_offsets")
         if skip:
@@ -438,7 +456,10 @@ class DevTreeGBM:
                                           _ptr(self.sums), _ptr(self.counts), s), "leaf_flag_sums_dev")
             return cur
         nxt = cur ^ 1
-        _ck(lh.h2o_part_compact_dev(_ptr(self.ridx[cur]), _ptr(self.pwork), _ptr(self.fbase), self.cap_p,
+        if d == 0 and self.root_ident:
+            # a root that stays a leaf is read back through ridx[0] when the depth is odd
+            _ck(lh.h2o_dt_root_leaf_iota(_ptr(recl), _ptr(self.ridx[0]), self.N, s), "dt_root_leaf_iota")
+        _ck(lh.h2o_part_compact_dev(self._ridx_ptr(d, cur), _ptr(self.pwork), _ptr(self.fbase), self.cap_p,
                                     _ptr(self.flags), _ptr(self.loff), _ptr(self.roff), _ptr(self.ridx[nxt]),
                                     _ptr(self.pos[cur]), _ptr(self.pos[nxt]), _ptr(self.counts), s),
             "part_compact_dev")
@@ -454,7 +475,8 @@ class DevTreeGBM:
         f = drv._f[:, 0]
         _ck(lh.h2o_gbm_grad(_ptr(self._y), _ptr(f), _ptr(self.wbuf) if self.sampled else None,
                             1 if self.bern else 0, self.N, _ptr(self.pos[0]), _ptr(self.dbuf), s), "gbm_grad")
-        _ck(lh.h2o_iota_i32(_ptr(self.ridx[0]), self.N, s), "iota")
+        if not self.root_ident:
+            _ck(lh.h2o_iota_i32(_ptr(self.ridx[0]), self.N, s), "iota")
         self.rec.zero_()
         self.sums.zero_()
         _ck(lh.h2o_dt_root(_ptr(self.rec), self.N, _stream()), "dt_root")

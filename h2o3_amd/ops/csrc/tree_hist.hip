@@ -367,6 +367,7 @@ struct QuadArgs {
   const uint8_t* cc; int Fp; const int* ridx; const float* va; const float* vb; const int4* wk;
   int n_work, n_fg, fgw, F, foff, Bs; float s0, s1; double* hist; int n_slots; double* wyy; long long bq;
   const uint8_t* need; const int* n_work_dev; unsigned long long* part = nullptr;
+  int t_lw = 0, t_lpr = 0, t_ss = 0;   // hist_bm_kernel: ragged mapping of the last group (t_lw = 0: none)
 };
 
 template <int M, bool V, bool PV, bool PK, bool PIPE = true, int LW = 1>
@@ -479,43 +480,36 @@ __device__ __forceinline__ unsigned long long fx_signed(float v, float s) {
   return (unsigned long long)(__double_as_longlong(d) - 0x4338000000000000LL);
 }
 
-template <int G, int CL, int MODE, bool HAS_VB, bool POSV, bool PACK, int LW = 2>
-__global__ __launch_bounds__(1024) void hist_bm_kernel(
+// Ragged last group (RAG, one-channel G = 64 layouts): a last group of nf < G
+// features runs with LPR = ceil(nf / NK) lanes per row (run-time, workgroup-
+// uniform) instead of G / NK, so no lane spends its LDS atomics on the
+// padding codes past F: RPW = 64 / LPR rows per wave instruction, the lanes
+// past RPW * LPR idle (their first position is the segment end).  Code kk of
+// lane q goes to slot kk*SS + q; SS = 16 puts the <= 4 rows of a 16-lane
+// group on distinct slots mod 16 for LPR >= 4 (SS = LPR does not: LPR = 9
+// slots 32..35 alias banks 0..3).  The bin-row pitch stays G.  F = 100: the
+// second group holds 36 features -> 9 lanes x 7 rows, 4 atomic instructions
+// per 7 rows where the full-width mapping issues 8 per 8 rows.  Bit-identical
+// histograms (integer LDS sums), measured slower: see g_bm_ragged below.
+template <int G, int CL, int MODE, bool HAS_VB, bool POSV, bool PACK, int LW, bool IDENT, bool RAG, bool MASK = false>
+__device__ __forceinline__ void hist_bm_body(
     const uint8_t* __restrict__ codes, int Fp, const int* __restrict__ ridx,
-    const float* __restrict__ va, const float* __restrict__ vb,
-    const int4* __restrict__ work, int n_work, int n_fg, int F, int foff, int Bs, float s0, float s1,
-    double* __restrict__ hist, int n_slots, double* __restrict__ wyy_out, long long bq,
-    const uint8_t* __restrict__ need, const int* __restrict__ n_work_dev, unsigned long long* __restrict__ part,
-    int dbg) {
+    const float* __restrict__ va, const float* __restrict__ vb, int4 wk, int lb, int fgi, int n_fg, int fg0, int nf,
+    int Bs, float s0, float s1, double* __restrict__ hist, int n_slots, double* __restrict__ wyy_out, long long bq,
+    unsigned long long* __restrict__ part, int dbg, int t_lpr, int t_ss) {
   constexpr int C = Chan<MODE>::C;
   constexpr int NK = 4 * LW;              // codes per lane (LW dwords)
-  constexpr int LPR = G / NK;             // lanes per row
-  constexpr int RPW = 64 / LPR;           // rows per wave instruction
+  const int LPR = RAG ? t_lpr : G / NK;   // lanes per row
+  const int SS = RAG ? t_ss : G / NK;     // slot stride between a lane's codes
+  const int RPW = 64 / LPR;               // rows per wave instruction
   constexpr int PITCH = G * CL;           // u64 entries per bin row
   constexpr int U = 4;                    // rows per lane per iteration
   constexpr int PD = 2;                   // iterations in the load ring
   using CT = typename CodeW<LW>::T;
   static_assert(CL == 1 || C == 2, "two LDS channels need a two-channel mode");
-  static_assert(LPR >= 1, "group narrower than one lane's codes");
+  static_assert(G / NK >= 1, "group narrower than one lane's codes");
+  // the kernel's dynamic LDS, declared here too: its address stays a compile-time constant
   extern __shared__ __attribute__((aligned(16))) unsigned long long ldsq[];
-  const int nwg = n_work_dev != nullptr ? n_work_dev[1] * n_fg : n_work * n_fg;
-  if ((int)blockIdx.x >= nwg) return;
-  const int lb = xcd_remap(blockIdx.x, nwg);
-  const int fgi = lb % n_fg;
-  int4 wk = work[lb / n_fg];
-  // workgroup-uniform: keep the segment in SGPRs (the buffer descriptors below need it there)
-  wk.x = __builtin_amdgcn_readfirstlane(wk.x);
-  wk.y = __builtin_amdgcn_readfirstlane(wk.y);
-  wk.z = __builtin_amdgcn_readfirstlane(wk.z);
-  if (need != nullptr && need[(size_t)wk.x * n_fg + fgi] == 0) return;   // no eligible feature in this group
-  const int fg0 = foff + fgi * G;
-  const int nf = min(G, F - fg0);
-  {
-    const int n2 = Bs * PITCH / 2;
-    ulonglong2* z = reinterpret_cast<ulonglong2*>(ldsq);
-    for (int i = threadIdx.x; i < n2; i += blockDim.x) z[i] = make_ulonglong2(0ull, 0ull);
-  }
-  __syncthreads();
   const int lane = threadIdx.x & 63;
   const int q = lane % LPR;
   const int rs = lane / LPR;
@@ -523,20 +517,23 @@ __global__ __launch_bounds__(1024) void hist_bm_kernel(
   const int nwaves = __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6));
   // atomic k of a row takes code kk = (k & ~3) | ((k + rs) & 3) of the lane's
   // NK codes (the dword is fixed by k, the byte rotates with the row) into
-  // slot kk*LPR + q: the rows of an LDS lane group hit disjoint slots
-  unsigned sh[NK], sb[NK];
+  // slot kk*SS + q: the rows of an LDS lane group hit disjoint slots
+  unsigned sh[NK], sb[NK], vm = 0;
 #pragma unroll
   for (int k = 0; k < NK; ++k) {
     const int kk = (k & ~3) | ((k + rs) & 3);
     sh[k] = 8u * kk;
-    sb[k] = (unsigned)((kk * LPR + q) * 8);
+    sb[k] = (unsigned)((kk * SS + q) * 8);
+    // MASK: the full-width mapping, minus the atomics of the padding codes past nf
+    if (MASK && NK * q + kk < nf) vm |= 1u << k;
   }
   const bool blk_wyy = MODE == 0 && wyy_out != nullptr && fgi == 0;   // workgroup-uniform
   double wyyd = 0.0;
   const int pend = wk.y + wk.z;
   const int step = nwaves * RPW;
   const uint8_t* cbase = codes + fg0 + NK * q;
-  const int p_first = wk.y + wv * RPW + rs;
+  // RAG: the lanes past the last whole row of the wave start at the segment end (no rows)
+  const int p_first = (RAG && rs >= RPW) ? pend : wk.y + wv * RPW + rs;
   const unsigned long long pk_off = (1ull << 40) + (unsigned long long)bq;   // count 1 + response bias
   // position-indexed arrays through buffer descriptors sized to [0, pend):
   // loads past the segment return 0 (no clamp), the row offset is one VGPR
@@ -553,9 +550,15 @@ __global__ __launch_bounds__(1024) void hist_bm_kernel(
   int R[PD][U];
   CT CW[PD][U];
   float XA[PD][U], XB[PD][U];
+  // IDENT (ridx == nullptr): the row id is the position (the root of a tree,
+  // ridx = iota): no load; positions past the segment take row 0, as the
+  // buffer loads return it
   auto load_r = [&](int p, int (&r)[U]) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) r[u] = __builtin_amdgcn_raw_buffer_load_b32(rr, p * 4, u * step * 4, 0);
+    for (int u = 0; u < U; ++u) {
+      if constexpr (IDENT) r[u] = p + u * step < pend ? p + u * step : 0;
+      else r[u] = __builtin_amdgcn_raw_buffer_load_b32(rr, p * 4, u * step * 4, 0);
+    }
   };
   auto load_v = [&](int p, const int (&r)[U], CT (&cw)[U], float (&xa)[U], float (&xb)[U]) {
 #pragma unroll
@@ -602,7 +605,7 @@ __global__ __launch_bounds__(1024) void hist_bm_kernel(
         } else {
           c0 = XB[d][u]; c1 = 0.f;
         }
-        if (!inr || (c0 == 0.f && c1 == 0.f) || (dbg & 2)) continue;
+        if (!inr || (c0 == 0.f && c1 == 0.f) || (dbg & 2) || (MASK && vm == 0)) continue;
         unsigned long long a0, a1 = 0ull;
         if (PACK) {
           // weights are 0/1: count 1, response y; the even magic constant of
@@ -614,6 +617,7 @@ __global__ __launch_bounds__(1024) void hist_bm_kernel(
         }
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
+          if (MASK && !((vm >> k) & 1u)) continue;
           unsigned word;
           if constexpr (LW == 2) word = (k & 4) ? CW[d][u].y : CW[d][u].x;
           else word = CW[d][u];
@@ -652,8 +656,9 @@ __global__ __launch_bounds__(1024) void hist_bm_kernel(
   for (int e = wv; e < nbq * NSG; e += nwaves) {
     const int b = (e / NSG) * 4 + bi;
     const int slot = (e % NSG) * 16 + si;
-    const int fl = NK * (slot % LPR) + slot / LPR;
-    if (b >= Bs || fl >= nf) continue;
+    const int sq = slot % SS, sk = slot / SS;     // slot = code sk of lane sq
+    const int fl = NK * sq + sk;
+    if (b >= Bs || sq >= LPR || sk >= NK || fl >= nf) continue;
     double* o = hist + ((size_t)(fg0 + fl) * n_slots + wk.x) * (size_t)(Bs * C) + (size_t)b * C;
     const unsigned long long v = ldsq[b * PITCH + slot];
     if (PACK) {
@@ -680,15 +685,97 @@ __global__ __launch_bounds__(1024) void hist_bm_kernel(
   }
 }
 
+// TLW: 0 = every group with the full-width mapping; 1 / 2 = the last group
+// runs the ragged mapping with TLW code dwords per lane when t_lpr > 0; 3 =
+// the last group runs the full-width mapping with the padding atomics masked
+// (workgroup-uniform branch: the groups of a work item stay adjacent
+// workgroups of one launch and share the row ids and the payload in L2).
+template <int G, int CL, int MODE, bool HAS_VB, bool POSV, bool PACK, int LW = 2, int TLW = 0, bool IDENT = false>
+__global__ __launch_bounds__(1024) void hist_bm_kernel(
+    const uint8_t* __restrict__ codes, int Fp, const int* __restrict__ ridx,
+    const float* __restrict__ va, const float* __restrict__ vb,
+    const int4* __restrict__ work, int n_work, int n_fg, int F, int foff, int Bs, float s0, float s1,
+    double* __restrict__ hist, int n_slots, double* __restrict__ wyy_out, long long bq,
+    const uint8_t* __restrict__ need, const int* __restrict__ n_work_dev, unsigned long long* __restrict__ part,
+    int dbg, int t_lpr, int t_ss) {
+  constexpr int PITCH = G * CL;           // u64 entries per bin row
+  extern __shared__ __attribute__((aligned(16))) unsigned long long ldsq[];
+  const int nwg = n_work_dev != nullptr ? n_work_dev[1] * n_fg : n_work * n_fg;
+  if ((int)blockIdx.x >= nwg) return;
+  const int lb = xcd_remap(blockIdx.x, nwg);
+  const int fgi = lb % n_fg;
+  int4 wk = work[lb / n_fg];
+  // workgroup-uniform: keep the segment in SGPRs (the buffer descriptors below need it there)
+  wk.x = __builtin_amdgcn_readfirstlane(wk.x);
+  wk.y = __builtin_amdgcn_readfirstlane(wk.y);
+  wk.z = __builtin_amdgcn_readfirstlane(wk.z);
+  if (need != nullptr && need[(size_t)wk.x * n_fg + fgi] == 0) return;   // no eligible feature in this group
+  const int fg0 = foff + fgi * G;
+  const int nf = min(G, F - fg0);
+  {
+    const int n2 = Bs * PITCH / 2;
+    ulonglong2* z = reinterpret_cast<ulonglong2*>(ldsq);
+    for (int i = threadIdx.x; i < n2; i += blockDim.x) z[i] = make_ulonglong2(0ull, 0ull);
+  }
+  __syncthreads();
+  if constexpr (TLW == 3) {
+    if (fgi == n_fg - 1) {
+      hist_bm_body<G, CL, MODE, HAS_VB, POSV, PACK, LW, IDENT, false, true>(codes, Fp, ridx, va, vb, wk, lb, fgi, n_fg,
+                                                                     fg0, nf, Bs, s0, s1, hist, n_slots, wyy_out, bq,
+                                                                     part, dbg, 0, 0);
+      return;
+    }
+  } else if constexpr (TLW != 0) {
+    if (t_lpr > 0 && fgi == n_fg - 1) {
+      hist_bm_body<G, CL, MODE, HAS_VB, POSV, PACK, TLW, IDENT, true>(codes, Fp, ridx, va, vb, wk, lb, fgi, n_fg, fg0,
+                                                               nf, Bs, s0, s1, hist, n_slots, wyy_out, bq, part, dbg,
+                                                               t_lpr, t_ss);
+      return;
+    }
+  }
+  hist_bm_body<G, CL, MODE, HAS_VB, POSV, PACK, LW, IDENT, false>(codes, Fp, ridx, va, vb, wk, lb, fgi, n_fg, fg0, nf,
+                                                           Bs, s0, s1, hist, n_slots, wyy_out, bq, part, dbg, 0, 0);
+}
+
 // microbenchmark phase switches (scripts/hist_bm_mb.py): 1 = no flush, 2 = no
 // LDS atomics, 4 = flush with integer atomics.  Results are wrong with any
 // bit set; 0 in production.
 static int g_bm_dbg = 0;
 extern "C" void h2o_hist_bm_set_debug(int flags) { g_bm_dbg = flags; }
 
-template <int G, int CL, int M, bool V, bool PV, bool PK, int LW>
+// Ragged last group (h2o_hist_bm_set_ragged): 0 = off (default); 1 = 4 codes
+// per lane, slot stride 16; 2 = 4 codes per lane, slot stride = lanes per row;
+// 3 = 8 codes per lane, slot stride 8; 4 = the full-width mapping with the
+// atomics of the padding codes masked.  Off by default: every variant is
+// SLOWER at 100M x 100 (root 3.4 -> 4.1-4.3 ms, profiles/README.md): the two
+// groups of a work item share each 128-B row through L2 only while they run
+// at the same pace, and a last group that runs ahead makes the other one
+// fetch the rows from HBM again.  Kept for frames and parts where that
+// changes.  A setter, not a static: tests flip it in one process.
+static int g_bm_ragged = 0;
+extern "C" void h2o_hist_bm_set_ragged(int mode) { g_bm_ragged = mode; }
+
+// Mapping of the last group: codes-per-lane dwords (0: full width), lanes per row, slot stride.
+struct BmTail { int lw, lpr, ss; };
+static BmTail bm_tail(int F, int foff, int Fp, int G, int CL, int n_fg) {
+  BmTail t{0, 0, 0};
+  const int fg0 = foff + (n_fg - 1) * G, nf = F - fg0;
+  if (g_bm_ragged <= 0 || g_bm_ragged > 4 || G != 64 || CL != 1 || nf >= G) return t;
+  if (g_bm_ragged == 4) return BmTail{3, 0, 0};   // full-width lanes, padding atomics masked: decode unchanged
+  if (g_bm_ragged == 3) {
+    const int l = (nf + 7) / 8;
+    // 8 atomic instructions per 64/l rows beat the full width's 8 per 8 rows for l <= 7
+    if (l <= 7 && fg0 + 8 * l <= Fp) return BmTail{2, l, 8};
+  }
+  const int l = (nf + 3) / 4;
+  // 4 atomic instructions per 64/l rows: no better than 1 per row above 12 lanes
+  if (l > 12) return t;
+  return BmTail{1, l, g_bm_ragged == 2 ? l : 16};
+}
+
+template <int G, int CL, int M, bool V, bool PV, bool PK, int LW, int TLW = 0, bool ID = false>
 static int lbm_u(const QuadArgs& a) {
-  auto kern = hist_bm_kernel<G, CL, M, V, PV, PK, LW>;
+  auto kern = hist_bm_kernel<G, CL, M, V, PV, PK, LW, TLW, ID>;
   static bool attr = false;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -697,16 +784,35 @@ static int lbm_u(const QuadArgs& a) {
   }
   hipLaunchKernelGGL(kern, a.grid, dim3(a.threads), a.lds, a.s, a.cc, a.Fp, a.ridx, a.va, a.vb, a.wk, a.n_work,
                      a.n_fg, a.F, a.foff, a.Bs, a.s0, a.s1, a.hist, a.n_slots, a.wyy, a.bq, a.need, a.n_work_dev,
-                     a.part, g_bm_dbg);
+                     a.part, g_bm_dbg, a.t_lpr, a.t_ss);
   return (int)hipGetLastError();
 }
 
 // H2O3_HIST_BM_LW: codes per lane (1 -> 4, 2 -> 8; A/B of the per-row work amortisation)
-template <int G, int CL, int M, bool V, bool PV, bool PK>
-static int lbm(const QuadArgs& a) {
+// ID: no row ids (a.ridx == nullptr), the instances of the device tree's root
+template <int G, int CL, int M, bool V, bool PV, bool PK, bool ID>
+static int lbm_t(const QuadArgs& a) {
   static const int lw = env_int("H2O3_HIST_BM_LW", 2);
+  if constexpr (G == 64 && CL == 1) {
+    // ragged last group: one more instance per tail width (h2o_hist_bm sets
+    // t_lw only with the default 8 codes per lane in the full groups)
+    if (a.t_lw == 1) return lbm_u<G, CL, M, V, PV, PK, 2, 1, ID>(a);
+    if (a.t_lw == 2) return lbm_u<G, CL, M, V, PV, PK, 2, 2, ID>(a);
+    if (a.t_lw == 3) return lbm_u<G, CL, M, V, PV, PK, 2, 3, ID>(a);
+  }
+  if constexpr (ID) return lbm_u<G, CL, M, V, PV, PK, 2, 0, true>(a);
   // G = 16: 8 rows share a 16-lane group, too many for 4 byte rotations -> 4 codes per lane
   return (lw == 1 || G == 16) ? lbm_u<G, CL, M, V, PV, PK, 1>(a) : lbm_u<G, CL, M, V, PV, PK, 2>(a);
+}
+
+template <int G, int CL, int M, bool V, bool PV, bool PK>
+static int lbm(const QuadArgs& a) {
+  if (a.ridx == nullptr) {
+    // h2o_hist_bm admits a null ridx for G = 64, one channel, position-ordered payloads only
+    if constexpr (G == 64 && CL == 1 && PV) return lbm_t<G, CL, M, V, PV, PK, true>(a);
+    return (int)hipErrorInvalidValue;
+  }
+  return lbm_t<G, CL, M, V, PV, PK, false>(a);
 }
 
 template <int G, int CL, int M, bool PK>
@@ -738,7 +844,7 @@ __global__ __launch_bounds__(256) void hist_bm_reduce_kernel(
     const unsigned long long* __restrict__ part, const int4* __restrict__ work, int n_work,
     const int* __restrict__ n_work_dev, int n_fg, int F, int foff, int G, int CL, int lpr, int nk, int Bs, int C,
     int pack, long long bq, float s0, float s1, const uint8_t* __restrict__ need, double* __restrict__ hist,
-    int n_slots) {
+    int n_slots, int t_lpr, int t_nk, int t_ss) {
   const int nw = n_work_dev != nullptr ? n_work_dev[1] : n_work;
   const int i0 = blockIdx.z * BM_RED;
   if (i0 >= nw) return;
@@ -751,8 +857,12 @@ __global__ __launch_bounds__(256) void hist_bm_reduce_kernel(
   const int sl = (blockIdx.x / nbt) * 16 + (threadIdx.x & 15);
   const int ch = sl / G, slot = sl - ch * G;
   const int fg0 = foff + g * G;
-  const int fl = nk * (slot % lpr) + slot / lpr;
-  const bool live = fl < min(G, F - fg0);
+  // slot = code sk of lane sq; the ragged last group (t_lpr > 0) has its own (lanes, codes, slot stride)
+  int ss = lpr;
+  if (t_lpr > 0 && g == n_fg - 1) { lpr = t_lpr; nk = t_nk; ss = t_ss; }
+  const int sq = slot % ss, sk = slot / ss;
+  const int fl = nk * sq + sk;
+  const bool live = sq < lpr && sk < nk && fl < min(G, F - fg0);
   const double inv0 = 1.0 / (double)s0, inv1 = 1.0 / (double)s1;
   const size_t E = (size_t)Bs * PITCH;
   const size_t eoff = (size_t)b * PITCH + sl;
@@ -813,17 +923,23 @@ extern "C" int h2o_hist_bm(const void* codes, int Fp, const int* ridx, const flo
   a.n_work = n_work; a.n_fg = n_fg; a.fgw = G; a.F = F; a.foff = foff; a.Bs = Bs; a.s0 = s0; a.s1 = s1;
   a.hist = hist; a.n_slots = n_slots; a.wyy = wyy; a.bq = pack_bq; a.need = need; a.n_work_dev = n_work_dev;
   a.part = part;
+  static const int lw_env = env_int("H2O3_HIST_BM_LW", 2);
+  const int lw = (lw_env == 1 || G == 16) ? 1 : 2;   // as lbm() picks it
+  const BmTail tail = lw == 2 ? bm_tail(F, foff, Fp, G, CL, n_fg) : BmTail{0, 0, 0};
+  // ridx == nullptr: row id = position (the root of a tree); one-channel G = 64
+  // layouts with position-ordered payloads and 8 codes per lane only
+  if (ridx == nullptr && !(G == 64 && CL == 1 && posv != 0 && lw == 2)) return -5;
+  a.t_lw = tail.lw; a.t_lpr = tail.lpr; a.t_ss = tail.ss;
   const int rc = G == 64 ? lbm_g<64>(mode, pack, vb != nullptr, posv != 0, a)
                : G == 32 ? lbm_g<32>(mode, pack, vb != nullptr, posv != 0, a)
                          : lbm_g<16>(mode, pack, vb != nullptr, posv != 0, a);
   if (rc != 0 || part == nullptr || (g_bm_dbg & 1)) return rc;
-  static const int lw_env = env_int("H2O3_HIST_BM_LW", 2);
-  const int lw = (lw_env == 1 || G == 16) ? 1 : 2;   // as lbm() picks it
   const int nk = 4 * lw, lpr = G / nk;
   const int C = mode == 2 ? 1 : 2;
   dim3 rg(((Bs + 15) / 16) * (G * CL / 16), n_fg, (n_work + BM_RED - 1) / BM_RED);
   hipLaunchKernelGGL(hist_bm_reduce_kernel, rg, dim3(256), 0, s, part, (const int4*)work, n_work, n_work_dev, n_fg,
-                     F, foff, G, CL, lpr, nk, Bs, C, pack ? 1 : 0, pack_bq, s0, s1, need, hist, n_slots);
+                     F, foff, G, CL, lpr, nk, Bs, C, pack ? 1 : 0, pack_bq, s0, s1, need, hist, n_slots,
+                     tail.lpr, 4 * tail.lw, tail.ss);
   return (int)hipGetLastError();
 }
 
@@ -1027,7 +1143,10 @@ __global__ __launch_bounds__(256) void part_flags_kernel(
   for (int base = wk.y; base < end; base += 256 * U) {
     int r[U], c[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) r[u] = ridx[min(base + u * 256 + (int)threadIdx.x, end - 1)];
+    for (int u = 0; u < U; ++u) {
+      const int pc = min(base + u * 256 + (int)threadIdx.x, end - 1);
+      r[u] = ridx != nullptr ? ridx[pc] : pc;     // nullptr: row id = position (the root of a tree)
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) c[u] = (int)codes[(size_t)r[u] * rs + (size_t)f * fs];
 #pragma unroll
@@ -1073,7 +1192,7 @@ __global__ __launch_bounds__(256) void part_compact_kernel(
     for (int u = 0; u < U; ++u) {
       const int p = base + u * 256 + (int)threadIdx.x;
       const int pc = min(p, end - 1);
-      r[u] = ridx[pc];
+      r[u] = ridx != nullptr ? ridx[pc] : pc;     // nullptr: row id = position (the root of a tree)
       a[u] = pa ? pa[pc] : 0.f;
       const int w0 = base + u * 256 + wv * 64;
       bal[u] = (w0 < end) ? flags[fb + (w0 - wk.y) / 64] : 0ull;
@@ -2287,6 +2406,18 @@ __global__ void dt_root_kernel(double* __restrict__ rec, long long N) {
   if (threadIdx.x == 0) { rec[DT_ST] = 0.0; rec[DT_CT] = (double)N; }
 }
 
+// Id-free root (the root kernels ran with a null ridx, nothing wrote iota): a
+// root that does NOT split stays the tree's only leaf, and its rows are read
+// back from either row-id buffer, whichever the level parity ends on --
+// buffer 0 then has to hold iota.  Every workgroup leaves at once when the
+// root splits (the usual case: a few us per tree).
+__global__ __launch_bounds__(256) void dt_root_leaf_iota_kernel(const double* __restrict__ rec,
+                                                                int* __restrict__ ridx0, long long n) {
+  if (rec[DT_OK] > 0.0) return;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    ridx0[i] = (int)i;
+}
+
 // Leaf sums of the level-D leaves WITHOUT compacting the last level: the
 // level-(D-1) payload is streamed in its own order and every row goes to the
 // left / right child of its slot by its go-left flag bit (part_flags_kernel's
@@ -2599,6 +2730,14 @@ int h2o_dt_leaf_vals(double* rec, const double* sums, int nh, int D, const float
 
 int h2o_dt_root(double* rec, long long N, hipStream_t s) {
   hipLaunchKernelGGL(dt_root_kernel, dim3(1), dim3(64), 0, s, rec, N);
+  return (int)hipGetLastError();
+}
+
+// After level 0's split selection: iota into ridx0[0, n) when the root is a leaf.
+int h2o_dt_root_leaf_iota(const double* rec, int* ridx0, long long n, hipStream_t s) {
+  if (n <= 0) return 0;
+  const long long blocks = std::min<long long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(dt_root_leaf_iota_kernel, dim3((unsigned)blocks), dim3(256), 0, s, rec, ridx0, n);
   return (int)hipGetLastError();
 }
 

@@ -181,8 +181,25 @@ def _lib():
                                          _c_void, _c_int, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void,
                                          _c_void, _c_void]
         lib.h2o_fill_nid.argtypes = [_c_void, _c_void, _c_int, _c_void, _c_void]
+        lib.h2o_hist_bm_set_ragged.argtypes = [_c_int]
+        lib.h2o_hist_bm_set_ragged.restype = None
         lib._typed = True
     return lib
+
+
+def bm_ragged() -> int:
+    """H2O3_HIST_BM_RAGGED: lane mapping of a last feature group narrower than
+    G in hist_bm_kernel.  0 (default): the full-width mapping; 1: dense lanes,
+    4 codes per lane, slot stride 16; 2 / 3 / 4: slot stride = lanes per row /
+    8 codes per lane / full width with the padding atomics masked.  Same bits
+    all; the dense mappings measured slower at 100M x 100 (profiles/README.md)."""
+    return int(env("H2O3_HIST_BM_RAGGED", "0"))
+
+
+def set_bm_ragged(lib, mode=None):
+    """Hand the switch to the library before a h2o_hist_bm launch (every
+    caller does, so the value of one caller never leaks into another's)."""
+    lib.h2o_hist_bm_set_ragged(bm_ragged() if mode is None else int(mode))
 
 
 def channels(mode: int) -> int:
@@ -419,6 +436,7 @@ def hist_build(bd, ridx, va, vb, mode, starts, counts, n_slots, use_native=None,
             need = _need(fgw)
             if bm is not None:
                 part = bm_part(len(items), n_fg, bd.Bs, fgw, pack or mode == 2, dev)
+                set_bm_ragged(lib)
                 rc = lib.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), len(items),
                                      bd.F, 0, bd.Bs, s0, s1, _ptr(hist), n_slots, mode, _ptr(wyy), 1 if posv else 0,
                                      bq, fgw, _ptr(need), None, _ptr(part), _stream())
@@ -945,6 +963,7 @@ def hist_build_dev(bd, ridx, va, vb, mode, rec, rec_cols, starts, counts, vmax, 
         s1, bq = _pack_scale(vmax[1] if vb is None else max(vmax[1], 0.0), chunk)
     if bm is not None:
         part = bm_part(cap, n_fg, bd.Bs, fgw, pack or mode == 2, dev)
+        set_bm_ragged(lib)
         rc = lib.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), cap, bd.F, 0, bd.Bs,
                              s0, s1, _ptr(Hb), n, mode, _ptr(wyy), 1 if posv else 0, bq, fgw, None, _ptr(cnts),
                              _ptr(part), _stream())

@@ -1,5 +1,6 @@
 """Micro-benchmark of the bin-major histogram kernel by level shape and phase
-(h2o_hist_bm_set_debug: 1 = no flush, 2 = no LDS atomics, 3 = loads only)."""
+(h2o_hist_bm_set_debug: 1 = no flush, 2 = no LDS atomics, 3 = loads only),
+for every lane mapping of the ragged last group (RAGGED=0,1,2,3: H2O3_HIST_BM_RAGGED)."""
 import ctypes
 import os
 import sys
@@ -18,6 +19,7 @@ for N in (12_500_000, 100_000_000):
     dev = "cuda"
     bd = BinnedData()
     bd.codes = torch.randint(0, 254, (N, Fp), dtype=torch.uint8, device=dev)
+    bd.codes[:, F:] = Bs - 1          # the padding columns hold the NA code, as in a binned frame
     bd.F, bd.Fp, bd.Bs, bd.code_bytes, bd.nrows_local = F, Fp, Bs, 1, N
     va = torch.randn(N, device=dev)
     vmax = tree_ops.channel_max(va, None, 0)
@@ -33,8 +35,10 @@ for N in (12_500_000, 100_000_000):
             st.append(st[-1] + c)
         b = list(range(0, nodes, 2))
         shapes.append((f"depth {d} ({len(b)} nodes, half rows)", order, [st[i] for i in b], [cnt[i] for i in b]))
-    for (name, ridx, starts, counts), tb in [(sh, tb) for sh in shapes
-                                             for tb in os.environ.get("TBS", "default").split(",")]:
+    for (name, ridx, starts, counts), tb, rag in [(sh, tb, rag) for sh in shapes
+                                                  for tb in os.environ.get("TBS", "default").split(",")
+                                                  for rag in os.environ.get("RAGGED", "0,1,2,3").split(",")]:
+        os.environ["H2O3_HIST_BM_RAGGED"] = rag
         if tb == "default":
             os.environ.pop("H2O3_HIST_TB", None)
             os.environ.pop("H2O3_HIST_CHUNK", None)
@@ -43,7 +47,7 @@ for N in (12_500_000, 100_000_000):
             os.environ["H2O3_HIST_CHUNK"] = tb[1:]
         else:
             os.environ["H2O3_HIST_TB"] = tb
-        name = f"{name} TB={tb}"
+        name = f"{name} TB={tb} ragged={rag}"
         line = []
         for flag in (0, 1, 2, 3, 5):
             os.environ["H2O3_HIST_BM_RED"] = "0" if flag == 5 else "1"
@@ -57,7 +61,7 @@ for N in (12_500_000, 100_000_000):
             torch.cuda.synchronize()
             line.append((time.perf_counter() - t) / 5 * 1e3)
         lib.h2o_hist_bm_set_debug(0)
-        print(f"N={N/1e6:g}M {name:44s} full {line[0]:7.3f}  no-flush {line[1]:7.3f}  no-atomics {line[2]:7.3f}  "
+        print(f"N={N/1e6:g}M {name:54s} full {line[0]:7.3f}  no-flush {line[1]:7.3f}  no-atomics {line[2]:7.3f}  "
               f"loads-only {line[3]:7.3f}  atomic-flush {line[4]:7.3f} ms", flush=True)
     del bd, va, shapes
     torch.cuda.empty_cache()
