@@ -342,7 +342,7 @@ class H2OGenericEstimator(H2OEstimator):
             raise ValueError("output_space and output_per_reference can only be used with a background_frame")
         if self._ncls > 2:
             raise ValueError("Calculating contributions is currently not supported for multinomial models.")
-        from .tree.shap import forest_contributions
+        from .tree.shap import shap_dispatch
         X = self._score_matrix(test_data)
         F = len(self._x)
         trees = [t for t, k in zip(self._forest.trees, self._forest.tclass) if k == 0]
@@ -351,10 +351,10 @@ class H2OGenericEstimator(H2OEstimator):
             return self._background_contributions(test_data, X, background_frame, top_n, bottom_n, compare_abs,
                                                   output_space, output_per_reference)
         if algo in ("gbm", "xgboost"):
-            phi = forest_contributions(trees, X, F)
+            phi = shap_dispatch(self, self._forest, X, F)
             phi[:, -1] += float(self._init_f[0])
         else:
-            phi = forest_contributions(trees, X, F, scale=1.0 / max(1, len(trees)))
+            phi = shap_dispatch(self, self._forest, X, F, scale=1.0 / max(1, len(trees)))
             if self._ncls == 2 and self._binomial_single:
                 r = 1.0 / (F + 1)
                 phi = r - phi if self._p0_trees else phi + r

@@ -13,6 +13,12 @@ over all rows at once instead of a per-row recursion.  Both children are
 visited with one-fraction = "row goes this way" (0/1 per row), which is
 the vectorised form of the reference's hot/cold recursion.
 
+That recursion (`forest_contributions`) is the CPU path and the oracle.  On the
+GPU, where every one of its steps is a kernel launch, the models call
+`forest_path_contributions` instead: the same values, recursion-free over leaf
+paths (`shap_path_kernel` of ops/csrc/tree_shap.hip, work = rows x leaves).
+H2O3_TREE_SHAP=torch forces the recursion there too, for A/B runs.
+
 With a background frame (`background_frame=`) the contributions are baseline
 (interventional) SHAP instead: recursion-free over leaf paths, work = test
 rows x background rows x leaves, on the HIP kernels of ops/shap_ops.py.
@@ -135,6 +141,54 @@ def forest_contributions(trees, X: torch.Tensor, F: int, scale: float = 1.0) -> 
     return phi
 
 
+def forest_path_contributions(forest, X: torch.Tensor, F: int, scale: float = 1.0, tree_class: int = 0,
+                              info: dict | None = None) -> torch.Tensor:
+    """forest_contributions of `forest`'s trees of class `tree_class` without
+    the recursion: path-dependent TreeSHAP over the leaf-path table
+    (ops/shap_ops.path_shap: shap_path_kernel of tree_shap.hip on CUDA
+    tensors), plus the bias column, which does not depend on the rows and is
+    summed here as tree_shap does.  info (optional dict) gets "kernel" and
+    "why" of the ShapResult."""
+    import numpy as np
+    from ...ops import shap_ops
+    res = shap_ops.path_shap(forest.pack(X.device), forest.leaf_paths(X.device), X, F, vscale=scale,
+                             tree_class=tree_class)
+    if info is not None:
+        info["kernel"], info["why"] = res.kernel, res.why
+    bias = 0.0
+    for t, k in zip(forest.trees, forest.tclass):
+        if k != tree_class:
+            continue
+        cover = np.maximum(np.asarray(t.weight, dtype=np.float64), 0.0)
+        root = cover[0] if cover[0] > 0 else 1.0
+        leaf = np.asarray(t.left, dtype=np.int64) < 0
+        bias += float(np.sum(np.asarray(t.value, dtype=np.float64)[leaf] * cover[leaf] / root))
+    phi = res.phi
+    phi[:, -1] += scale * bias
+    return phi
+
+
+def shap_dispatch(owner, forest, X: torch.Tensor, F: int, scale: float = 1.0) -> torch.Tensor:
+    """Path-dependent contributions of the class-0 trees for a model's score
+    matrix: the kernel path on the GPU, the recursion on CPU tensors or with
+    H2O3_TREE_SHAP=torch (read at call time, for A/B runs).  Records on
+    `owner` why the kernel did not run (_shap_path_why, None when it did)."""
+    import os
+    why = None
+    if X.device.type != "cuda":
+        why = "CPU tensors"
+    elif os.environ.get("H2O3_TREE_SHAP", "") == "torch":
+        why = "H2O3_TREE_SHAP=torch"
+    if why is not None:
+        owner._shap_path_why = why
+        trees = [t for t, k in zip(forest.trees, forest.tclass) if k == 0]
+        return forest_contributions(trees, X, F, scale)
+    info = {}
+    phi = forest_path_contributions(forest, X, F, scale, 0, info)
+    owner._shap_path_why = info["why"]
+    return phi
+
+
 def background_contributions(forest, X, Z, F, vscale=1.0, bias=0.0, linkinv=None, output_space=False,
                              output_per_reference=False, max_scratch_bytes=1 << 30):
     """Baseline (interventional) SHAP of `forest`'s class-0 trees for the test
@@ -228,7 +282,7 @@ def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=Fals
             extra = list(zip(_pair_index_vecs(frame, X.shape[1], Z.shape[1], X.device),
                              ["RowIdx", "BackgroundRowIdx"]))
     elif model.algo == "drf":
-        phi = forest_contributions(trees, X, len(names), scale=1.0 / max(1, len(trees)))
+        phi = shap_dispatch(model, model._forest, X, len(names), scale=1.0 / max(1, len(trees)))
         if spec.nclasses == 2:
             # the reference's binomial DRF form (ScoreContributionsTaskDRF,
             # DRFModel.java:97-106: its trees score P(class 0)): 1/(F+1) -
@@ -237,7 +291,7 @@ def tree_contributions(model, frame, top_n=None, bottom_n=None, compare_abs=Fals
             phi[:, :-1] += r
             phi[:, -1] += r - 1.0
     else:
-        phi = forest_contributions(trees, X, len(names))
+        phi = shap_dispatch(model, model._forest, X, len(names))
         phi[:, -1] += float(model._init_f[0])
     from ..shap_baseline import contributions_frame
     return contributions_frame(phi, names, extra, top_n, bottom_n, compare_abs)

@@ -174,7 +174,11 @@ class Forest:
         Keys: leaf_val [L] f64, leaf_cls [L] i32, el_off [L+1], el_feat [E],
         cond_off [E+1], cond_node [C] i32, cond_left [C] u8, tree_leaf_off
         (host list, T+1), L, max_path (most elements of one leaf),
-        max_tree_leaves, max_feat (largest feature id split on, -1 if none)."""
+        max_tree_leaves, max_feat (largest feature id split on, -1 if none),
+        el_zero [E] f64 (path-dependent TreeSHAP's zero-fraction of the
+        element: the product over its conditions of cover[wanted child] /
+        cover[node], covers = max(Tree.weight, 0), a zero node cover counting
+        as 1)."""
         trees = self.trees if upto is None else self.trees[:upto]
         # keyed on the pack it indexes into: whatever drops the pack drops this too
         P = self.pack(device, upto)
@@ -182,7 +186,7 @@ class Forest:
         if cached is not None and cached[0] is P:
             return cached[1]
         # vectorised per tree: walk every leaf up to the root one level per step
-        lval, lcls, nel, efeat, ncond, cnode, cleft = [], [], [], [], [], [], []
+        lval, lcls, nel, efeat, ncond, cnode, cleft, ezero = [], [], [], [], [], [], [], []
         tree_leaf_off = [0]
         base = 0
         for ti, t in enumerate(trees):
@@ -200,7 +204,11 @@ class Forest:
             leaves = idx[~inner]
             cur = leaves.copy()
             who = np.arange(leaves.size, dtype=np.int64)
-            c_leaf, c_node, c_left = [], [], []
+            cover = np.maximum(np.asarray(t.weight, dtype=np.float64), 0.0)
+            if cover.size != n:                       # a tree without covers: every node counts 1
+                cover = np.ones(n, dtype=np.float64)
+            denom = np.where(cover > 0, cover, 1.0)
+            c_leaf, c_node, c_left, c_frac = [], [], [], []
             top = leaves.copy()                       # highest ancestor reached
             for _ in range(n):
                 p = parent[cur]
@@ -211,6 +219,7 @@ class Forest:
                 c_leaf.append(who)
                 c_node.append(p)
                 c_left.append(isleft[cur])
+                c_frac.append(cover[cur] / denom[p])
                 top[who] = p
                 cur = p
             keep = top == 0                           # leaves hanging off the root (drops orphan nodes)
@@ -219,20 +228,23 @@ class Forest:
                 cl_ = np.concatenate(c_leaf)
                 cn_ = np.concatenate(c_node)
                 cw_ = np.concatenate(c_left)
+                cz_ = np.concatenate(c_frac)
                 ok = keep[cl_]
-                cl_, cn_, cw_ = newid[cl_[ok]], cn_[ok], cw_[ok]
+                cl_, cn_, cw_, cz_ = newid[cl_[ok]], cn_[ok], cw_[ok], cz_[ok]
             else:
                 cl_ = cn_ = np.zeros(0, dtype=np.int64)
                 cw_ = np.zeros(0, dtype=np.uint8)
+                cz_ = np.zeros(0, dtype=np.float64)
             cf_ = f_[cn_]
             o = np.lexsort((cn_, cf_, cl_))           # by leaf, then feature, then node (root first)
-            cl_, cn_, cw_, cf_ = cl_[o], cn_[o], cw_[o], cf_[o]
+            cl_, cn_, cw_, cf_, cz_ = cl_[o], cn_[o], cw_[o], cf_[o], cz_[o]
             nl = int(keep.sum())
             first = np.ones(cl_.size, dtype=bool)
             first[1:] = (cl_[1:] != cl_[:-1]) | (cf_[1:] != cf_[:-1])
             starts = np.nonzero(first)[0]
             nel.append(np.bincount(cl_[starts], minlength=nl))
             efeat.append(cf_[starts])
+            ezero.append(np.multiply.reduceat(cz_, starts) if starts.size else np.zeros(0, dtype=np.float64))
             ncond.append(np.diff(np.append(starts, cl_.size)))
             cnode.append(cn_ + base)
             cleft.append(cw_)
@@ -254,6 +266,7 @@ class Forest:
               "leaf_cls": torch.as_tensor(cat(lcls, np.int32), device=d),
               "el_off": torch.as_tensor(offs(nel), device=d),
               "el_feat": torch.as_tensor(ef, device=d),
+              "el_zero": torch.as_tensor(cat(ezero, np.float64), device=d),
               "cond_off": torch.as_tensor(offs(ncond), device=d),
               "cond_node": torch.as_tensor(cat(cnode, np.int32), device=d),
               "cond_left": torch.as_tensor(cat(cleft, np.uint8), device=d),

@@ -13,6 +13,10 @@ contributes only when every element holds for x or for z; then with
 A = okx & ~okz (a elements) and B = okz & ~okx (b elements) each feature of A
 gets +v (a-1)! b! / (a+b)! and each feature of B gets -v a! (b-1)! / (a+b)!.
 Per pair the contributions sum to f(x) - f(z); the bias term is f(z).
+
+`path_shap` / `path_shap_torch` (end of the file) are path-dependent TreeSHAP,
+predict_contributions without a background frame, over the same leaf table:
+node covers take the place of the background rows.
 """
 from __future__ import annotations
 
@@ -37,7 +41,8 @@ def _ptr(t):
 
 
 class ShapResult:
-    """Result of `background_shap`.
+    """Result of `background_shap` (and of `path_shap`: fz None, bg_tiles 0,
+    bias column left at zero).
 
     phi          [N, F+1] (averaged) or [N*B, F+1] (per reference, ordered by
                  test row then background row) f64; last column = bias term
@@ -303,3 +308,149 @@ def background_shap(P, PT, X, Z, F, per_reference=False, vscale=1.0, tree_class=
         timing["masks_ms"] = sum(a.elapsed_time(b) for a, b, _ in events)
         timing["pairs_ms"] = sum(b.elapsed_time(c) for _, b, c in events)
     return ShapResult(phi, fz, True, None, row_tiles, bg_tiles, len(chunks))
+
+
+# ------------------------------------------------------------------ path-dependent TreeSHAP
+_path_tables: dict = {}
+
+
+def path_coef_table(device) -> torch.Tensor:
+    """C[k, i] = i! (k-1-i)! / k! for i < k <= 32 (else 0), [33, 32] f64: the
+    Shapley weight of a coalition of i of the other k-1 path elements.  Built
+    once per device."""
+    key = str(device)
+    if key not in _path_tables:
+        C = [[0.0] * MAX_PATH for _ in range(MAX_PATH + 1)]
+        for k in range(1, MAX_PATH + 1):
+            for i in range(k):
+                C[k][i] = float(Fraction(math.factorial(i) * math.factorial(k - 1 - i), math.factorial(k)))
+        _path_tables[key] = torch.tensor(C, dtype=torch.float64, device=device)
+    return _path_tables[key]
+
+
+def path_shap_torch(P, PT, X, F, vscale=1.0, tree_class=0):
+    """Path-dependent TreeSHAP (Lundberg et al., Algorithm 2) over leaf paths
+    in torch, vectorised over rows with a loop over leaves.  Returns phi
+    [N, F+1] f64 with the bias column left at zero.
+
+    For a leaf of value v with k path elements, element e has the feature
+    d_e, the one-fraction o_e in {0, 1} ("the row satisfies every condition
+    of the element") and the zero-fraction z_e = PT["el_zero"].  EXTEND
+    builds the path weights w[0..k] one element at a time; per element the
+    UNWOUND-SUM of models/tree/shap.py (_unwound_sum, both branches) times
+    (o_e - z_e) * v goes to column d_e."""
+    dev = X.device
+    X = X.to(torch.float32)
+    N = X.shape[1]
+    host = (PT["el_off"].tolist(), PT["cond_off"].tolist())
+    cls = PT["leaf_cls"].tolist()
+    val = PT["leaf_val"].tolist()
+    phi = torch.zeros((N, F + 1), dtype=torch.float64, device=dev)
+    for l in range(PT["L"]):
+        e0 = host[0][l]
+        k = host[0][l + 1] - e0
+        if cls[l] != tree_class or k == 0:
+            continue
+        O = _leaf_ok(P, PT, host, l, X).to(torch.float64)             # [k, N]
+        Z = PT["el_zero"][e0:e0 + k].view(k, 1)
+        idx = torch.arange(k + 1, dtype=torch.float64, device=dev).view(-1, 1)
+        w = torch.zeros((k + 1, N), dtype=torch.float64, device=dev)
+        w[0] = 1.0
+        for d in range(1, k + 1):                                      # EXTEND with element d-1
+            up = torch.zeros_like(w)
+            up[1:] = w[:-1] * (idx[1:] / (d + 1))                      # w[i] (i+1)/(d+1) into w[i+1]
+            w = Z[d - 1] * w * ((d - idx).clamp(min=0.0) / (d + 1)) + O[d - 1] * up
+        nz = O != 0
+        zok = Z != 0
+        zsafe = torch.where(zok, Z, torch.ones_like(Z))
+        nxt = w[k].expand(k, N).clone()
+        total = torch.zeros((k, N), dtype=torch.float64, device=dev)
+        for i in range(k - 1, -1, -1):                                 # UNWOUND-SUM of every element at once
+            tmp = nxt * (k + 1) / (i + 1)
+            t_zero = torch.where(zok, (w[i] / zsafe) / ((k - i) / (k + 1)), torch.zeros_like(tmp))
+            total = total + torch.where(nz, tmp, t_zero)
+            nxt = torch.where(nz, w[i] - tmp * Z * ((k - i) / (k + 1)), nxt)
+        c = total * (O - Z) * (float(vscale) * val[l])
+        phi.index_add_(1, PT["el_feat"][e0:e0 + k].long(), c.t())
+    return phi
+
+
+def _typed_path(lib):
+    if not getattr(lib, "_typed_path", False):
+        lib.h2o_shap_path.argtypes = [_c_void, _c_int] + [_c_void] * 5 + [_c_int] * 3 + \
+            [_c_void, _c_dbl, _c_void, _c_ll, _c_int, _c_void]
+        lib.h2o_shap_path_lds_bytes.restype = _c_ll
+        lib._typed_path = True
+    return _typed(lib)
+
+
+def path_shap(P, PT, X, F, vscale=1.0, tree_class=0, max_scratch_bytes=1 << 30, timing=None) -> ShapResult:
+    """Path-dependent TreeSHAP contributions of the F features for the rows X
+    [F, N] (column-major float32): phi [N, F+1] f64 whose bias column is left
+    at zero for the caller (it does not depend on the rows).
+
+    P, PT          Forest.pack() and Forest.leaf_paths() on X's device
+    vscale         factor on every leaf value (DRF: 1 / ntrees)
+    tree_class     only trees of this class are scored
+    max_scratch_bytes  bound on the mask scratch; rows and trees are tiled to fit
+    timing         optional dict: gets "masks_ms" / "path_ms", the two stages'
+                   device time from stream events (synchronises at the end)
+
+    On a GPU: shap_mask_kernel for the one-fractions, then shap_path_kernel
+    (csrc/tree_shap.hip).  `path_shap_torch` runs for CPU tensors and for
+    paths wider than the kernel's masks; the result then says why."""
+    N = int(X.shape[1])
+    if int(X.shape[0]) < F:
+        raise ValueError("path_shap: X must be [F, rows]")
+    if PT["max_feat"] >= F:
+        raise ValueError("path_shap: the forest splits on a feature the matrix does not have")
+    why = None
+    if X.device.type != "cuda":
+        why = "CPU tensors"
+    elif PT["max_path"] > MAX_PATH:
+        why = f"a path has {PT['max_path']} distinct features, the kernel's masks hold {MAX_PATH}"
+    if why is not None:
+        return ShapResult(path_shap_torch(P, PT, X, F, vscale, tree_class), None, False, why)
+    lib = _typed_path(_native.get_lib("tree_shap", required=True))
+    dev = X.device
+    X = X.contiguous().to(torch.float32)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    C = path_coef_table(dev)
+    rt, _, chunks = _plan(PT, N, 0, max_scratch_bytes, False)
+    phi = torch.zeros((N, F + 1), dtype=torch.float64, device=dev)
+    lmax = max(c[1] - c[0] for c in chunks) if chunks else 0
+    MX = torch.empty(lmax * rt, dtype=torch.int32, device=dev)
+    row_tiles = 0
+    events = []
+
+    def mark():
+        if timing is None:
+            return None
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+    for r0 in range(0, N, rt):
+        nr = min(rt, N - r0)
+        row_tiles += 1
+        base = ctypes.c_void_p(X.data_ptr() + 4 * r0)
+        for l0, l1 in chunks:
+            e0 = mark()
+            rc = lib.h2o_shap_masks(base, X.shape[1], nr, _ptr(P["node"]), _ptr(P["cat_off"]), _ptr(P["cat_len"]),
+                                    _ptr(P["cat_bits"]), _ptr(PT["el_off"]), _ptr(PT["el_feat"]),
+                                    _ptr(PT["cond_off"]), _ptr(PT["cond_node"]), _ptr(PT["cond_left"]),
+                                    _ptr(PT["leaf_val"]), _ptr(PT["leaf_cls"]), int(tree_class), l0, l1, _ptr(MX),
+                                    _ptr(None), float(vscale), stream)
+            if rc != 0:
+                raise RuntimeError(f"h2o_shap_masks failed: {rc}")
+            e1 = mark()
+            rc = lib.h2o_shap_path(_ptr(MX), nr, _ptr(PT["el_off"]), _ptr(PT["el_feat"]), _ptr(PT["el_zero"]),
+                                   _ptr(PT["leaf_val"]), _ptr(PT["leaf_cls"]), int(tree_class), l0, l1, _ptr(C),
+                                   float(vscale), _ptr(phi), r0, F, stream)
+            if rc != 0:
+                raise RuntimeError(f"h2o_shap_path failed: {rc}")
+            events.append((e0, e1, mark()))
+    if timing is not None:
+        torch.cuda.synchronize()
+        timing["masks_ms"] = sum(a.elapsed_time(b) for a, b, _ in events)
+        timing["path_ms"] = sum(b.elapsed_time(c) for _, b, c in events)
+    return ShapResult(phi, None, True, None, row_tiles, 0, len(chunks))
