@@ -1249,7 +1249,7 @@ class H2OEstimator:
         from .explain import partial_dependence
         return partial_dependence(self, data, cols or [], nbins=nbins, weight_column=weight_column,
                                   include_na=include_na, user_splits=user_splits, targets=targets,
-                                  row_index=row_index)
+                                  row_index=row_index, col_pairs_2dpdp=col_pairs_2dpdp)
 
     def permutation_importance(self, frame, metric="AUTO", n_samples=10000, n_repeats=1, features=None, seed=-1,
                                use_pandas=True):

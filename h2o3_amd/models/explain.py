@@ -9,14 +9,22 @@ permuted, n_repeats, n_samples), hex/tree/FriedmanPopescusH.java
 (explain() / explain_row() assemble varimp, SHAP summary, PDP/ICE,
 residual analysis, leaderboard).
 
-Everything here is built from the model's batched device predict(): one
-scoring pass per grid point / permutation, no per-row host work.  explain()
-returns the tables the reference plots and, with plot=True, the matplotlib
-figures too (models/explain_plots.py).
+Partial dependence (1-D and 2-D), ICE and the H statistic of a tree model
+(GBM, DRF, XGBoost gbtree, Generic with a device forest) run on the
+forest-grid primitive (ops/pd_ops.py, csrc/tree_pd.hip): the score matrix is
+built once and one launch scores every row on up to 64 grid points.
+H2O3_TREE_PD=torch forces the replacement loop (one batched device predict()
+per grid point), which every other model uses and which is the reference;
+model._pd_why says why the loop ran (None on the primitive).  Permutation
+importance is one scoring pass per permutation.  explain() returns the tables
+the reference plots and, with plot=True, the matplotlib figures too
+(models/explain_plots.py).
 """
 from __future__ import annotations
 
+import itertools
 import math
+import os
 
 import numpy as np
 import pandas as pd
@@ -35,7 +43,10 @@ def _replace(frame: H2OFrame, col: str, vec: Vec) -> H2OFrame:
 
 def _response(model, frame, target=None) -> torch.Tensor:
     """Per-row response used by PDP: p(class) for classifiers, predict otherwise."""
-    raw = model._predict_raw(frame)
+    return _resp_col(model, model._predict_raw(frame), target)
+
+
+def _resp_col(model, raw, target=None) -> torch.Tensor:
     spec = model._spec
     if spec is not None and spec.nclasses >= 2:
         dom = spec.response_domain
@@ -51,6 +62,11 @@ def _wstats(v: torch.Tensor, w: torch.Tensor | None):
     v, w = v[ok], w[ok]
     s = torch.stack([w.sum(), (w * v).sum(), (w * v * v).sum(), torch.tensor(float(v.numel()),
                                                                              dtype=v.dtype, device=v.device)])
+    return _wfinish(s)
+
+
+def _wfinish(s: torch.Tensor):
+    """(mean, stddev, std error) from this rank's [sum w, sum wv, sum wvv, n]."""
     coll.allreduce_(s)
     sw, sv, svv, n = (float(x) for x in s)
     mean = sv / sw if sw > 0 else float("nan")
@@ -81,34 +97,152 @@ def _grid(vec: Vec, nbins, user_split=None, include_na=False):
     return vals, labels
 
 
+def _grid_vec(vec: Vec, vals) -> Vec:
+    """One row per grid value of the column `vec`, typed as the replacement
+    loop types its constant column: enum codes (NaN = NA = -1) in the
+    column's own domain, numeric values cast to f32."""
+    dev = vec.data.device if isinstance(vec.data, torch.Tensor) else cloud.device()
+    if vec.type == T_ENUM:
+        return Vec(torch.tensor([-1 if v != v else int(v) for v in vals], dtype=torch.int32, device=dev),
+                   T_ENUM, vec.domain)
+    return Vec(torch.tensor([float(v) for v in vals], dtype=torch.float32, device=dev), T_REAL)
+
+
+def _const_frame(frame: H2OFrame, cols, vecs, point) -> H2OFrame:
+    """The replacement loop's frame: every column of `cols` constant at its
+    value of the grid point."""
+    for c, vec, v in zip(cols, vecs, point):
+        one = _grid_vec(vec, [v])
+        frame = _replace(frame, c, Vec(one.data.expand(frame.nlocal).contiguous(), one.type, one.domain))
+    return frame
+
+
+class _ForestGrid:
+    """Partial dependence of one frame on the forest-grid primitive
+    (ops/pd_ops.py): the score matrix is built once, rows are tiled so that a
+    tile's [64, rows, K] sums stay under max_scratch_bytes, and the model's
+    _raw_from_sums turns every tile's sums into raw predictions."""
+
+    def __init__(self, model, frame: H2OFrame, max_scratch_bytes=1 << 30):
+        self.model, self.frame, self.max_scratch_bytes = model, frame, int(max_scratch_bytes)
+        self._X = None
+
+    def names(self):
+        m = self.model
+        return list(m._x) if m.algo == "generic" else list(m._spec.x)
+
+    def why_not(self, cols):
+        """Why these columns run on the replacement loop (None: the primitive)."""
+        from ..ops import pd_ops
+        m = self.model
+        if os.environ.get("H2O3_TREE_PD", "").lower() == "torch":
+            return "H2O3_TREE_PD=torch"
+        if getattr(m, "_gblinear", None) is not None:
+            return "booster=gblinear has no trees"
+        if not hasattr(m, "_raw_from_sums") or getattr(m, "_forest", None) is None:
+            return f"{m.algo} is not a tree model with a device forest"
+        off = getattr(m._spec, "offset_column", None)
+        if off and off in self.frame.names:
+            return f"offset column {off} in the frame"
+        if len(cols) > pd_ops.MAX_COLS:
+            return f"{len(cols)} columns together, the primitive takes {pd_ops.MAX_COLS}"
+        if len(set(cols)) != len(cols):
+            return "a column is named twice"
+        names = self.names()
+        for c in cols:
+            if c not in names:
+                return f"column {c} is not a feature of the model"
+        depth = pd_ops.max_depth(m._forest.pack(cloud.device()))
+        if depth > pd_ops.MAX_DEPTH:
+            return f"the forest is {depth} splits deep, the kernel takes {pd_ops.MAX_DEPTH}"
+        return None
+
+    def X(self):
+        if self._X is None:
+            self._X = self.model._score_matrix(self.frame)
+        return self._X
+
+    def adapt(self, cols, vecs, axes):
+        """[S, G] f32 grid from per-column value lists (one entry per grid
+        point): the values pass through the model's own adaptation of the
+        column (_score_matrix of a G-row frame), so frame-domain enum codes
+        become training-domain codes and unseen levels / NA become NaN."""
+        names = self.names()
+        fr = H2OFrame.from_vecs([_grid_vec(v, a) for v, a in zip(vecs, axes)], list(cols))
+        return self.model._score_matrix(fr)[[names.index(c) for c in cols]]
+
+    def responses(self, cols, grid, targets=(None,)):
+        """Yields (g0, r0, [resp [gc, n] f64 per target]) over row tiles and
+        chunks of 64 grid points."""
+        from ..ops import pd_ops
+        m = self.model
+        names = self.names()
+        fidx = [names.index(c) for c in cols]
+        X = self.X()
+        K = int(m._K)
+        P = m._forest.pack(X.device)
+        N, G = int(X.shape[1]), int(grid.shape[1])
+        nt = max(1, self.max_scratch_bytes // (4 * K * min(max(G, 1), pd_ops.CHUNK)))
+        if nt >= 256:
+            nt -= nt % 256
+        for r0 in range(0, N, nt):
+            n = min(nt, N - r0)
+            for g0 in range(0, G, pd_ops.CHUNK):
+                gc = min(pd_ops.CHUNK, G - g0)
+                res = pd_ops.forest_grid_sums(P, X, K, fidx, grid[:, g0:g0 + gc], r0, n)
+                m._pd_why = res.why
+                raw = m._raw_from_sums(res.sums.view(gc * n, K))
+                yield g0, r0, [_resp_col(m, raw, t).view(gc, n) for t in targets]
+
+
+def _wsums_grid(resp: torch.Tensor, w: torch.Tensor | None) -> torch.Tensor:
+    """_wstats' sums for every row of resp [g, n]: [g, 4] f64."""
+    ok = ~torch.isnan(resp)
+    wv = ok.to(resp.dtype) if w is None else ok * w.view(1, -1)
+    v = torch.where(ok, resp, torch.zeros_like(resp))
+    return torch.stack([wv.sum(1), (wv * v).sum(1), (wv * v * v).sum(1), ok.sum(1).to(resp.dtype)], 1)
+
+
 def partial_dependence(model, frame: H2OFrame, cols, nbins=20, weight_column=None, include_na=False,
-                       user_splits=None, targets=None, row_index=None):
+                       user_splits=None, targets=None, row_index=None, col_pairs_2dpdp=None):
     """Returns one pandas DataFrame per column: [col, mean_response,
-    stddev_response, std_error_mean_response] (PartialDependence.java)."""
+    stddev_response, std_error_mean_response] (PartialDependence.java), then
+    one per pair of col_pairs_2dpdp: [col1, col2, mean_response, ...] over the
+    Cartesian product of the two columns' grids, col1 outer and col2 inner.
+    With `targets`, one table per column (pair) and target."""
     if isinstance(cols, str):
         cols = [cols]
+    sets = [[c] for c in (cols or [])]
+    for pair in col_pairs_2dpdp or []:
+        if isinstance(pair, str) or len(pair) != 2:
+            raise ValueError(f"col_pairs_2dpdp: every entry is a pair of column names, got {pair!r}")
+        sets.append([str(pair[0]), str(pair[1])])
     w = frame.vec(weight_column).as_float(torch.float64) if weight_column else None
     if row_index is not None:
         frame = frame[int(row_index), :]
         w = None
     out = []
-    tg = targets if targets else [None]
-    for c in cols:
-        vec = frame.vec(c)
-        vals, labels = _grid(vec, nbins, (user_splits or {}).get(c), include_na)
-        for t in tg:
-            rows = []
-            for v, lab in zip(vals, labels):
-                if vec.type == T_ENUM:
-                    code = -1 if v != v else int(v)
-                    nv = Vec(torch.full((frame.nlocal,), code, dtype=torch.int32, device=vec.data.device),
-                             T_ENUM, vec.domain)
-                else:
-                    nv = Vec(torch.full((frame.nlocal,), v, dtype=torch.float32, device=vec.data.device), T_REAL)
-                resp = _response(model, _replace(frame, c, nv), t)
-                m, sd, se = _wstats(resp, w)
-                rows.append((lab, m, sd, se))
-            df = pd.DataFrame(rows, columns=[c, "mean_response", "stddev_response", "std_error_mean_response"])
+    tg = list(targets) if targets else [None]
+    fg = _ForestGrid(model, frame)
+    stat_cols = ["mean_response", "stddev_response", "std_error_mean_response"]
+    for cs in sets:
+        vecs = [frame.vec(c) for c in cs]
+        axes = [_grid(v, nbins, (user_splits or {}).get(c), include_na) for c, v in zip(cs, vecs)]
+        points = list(itertools.product(*[list(zip(vals, labels)) for vals, labels in axes]))
+        model._pd_why = fg.why_not(cs)
+        if model._pd_why is None:
+            grid = fg.adapt(cs, vecs, [[p[s][0] for p in points] for s in range(len(cs))])
+            sums = [torch.zeros((len(points), 4), dtype=torch.float64, device=grid.device) for _ in tg]
+            for g0, r0, resp in fg.responses(cs, grid, tg):
+                for acc, r in zip(sums, resp):
+                    acc[g0:g0 + r.shape[0]] += _wsums_grid(r, None if w is None else w[r0:r0 + r.shape[1]])
+            stats = [[_wfinish(s) for s in acc] for acc in sums]
+        else:                                   # the replacement loop: one scoring pass per grid point
+            stats = [[_wstats(_response(model, _const_frame(frame, cs, vecs, [v for v, _ in p]), t), w)
+                      for p in points] for t in tg]
+        for t, st in zip(tg, stats):
+            rows = [tuple(lab for _, lab in p) + tuple(s) for p, s in zip(points, st)]
+            df = pd.DataFrame(rows, columns=list(cs) + stat_cols)
             if t is not None:
                 df.attrs["target"] = t
             out.append(df)
@@ -124,13 +258,19 @@ def ice(model, frame: H2OFrame, col, nbins=20, max_rows=50, seed=0):
     sub = frame[list(map(int, idx)), :]
     vec = sub.vec(col)
     vals, labels = _grid(vec, nbins)
+    fg = _ForestGrid(model, sub)
+    model._pd_why = fg.why_not([col])
+    if model._pd_why is None:
+        resp = torch.zeros((len(vals), sub.nlocal), dtype=torch.float64, device=cloud.device())
+        for g0, r0, (r,) in fg.responses([col], fg.adapt([col], [vec], [vals])):
+            resp[g0:g0 + r.shape[0], r0:r0 + r.shape[1]] = r
+        m = resp.shape[1]
+        return pd.DataFrame({"row": [int(i) for i in idx[:m]] * len(vals),
+                             col: [lab for lab in labels for _ in range(m)],
+                             "response": resp.reshape(-1).cpu().numpy()}, columns=["row", col, "response"])
     recs = []
     for v, lab in zip(vals, labels):
-        if vec.type == T_ENUM:
-            nv = Vec(torch.full((sub.nlocal,), int(v), dtype=torch.int32, device=vec.data.device), T_ENUM, vec.domain)
-        else:
-            nv = Vec(torch.full((sub.nlocal,), v, dtype=torch.float32, device=vec.data.device), T_REAL)
-        r = _response(model, _replace(sub, col, nv)).cpu().numpy()
+        r = _response(model, _const_frame(sub, [col], [vec], [v])).cpu().numpy()
         for i, rv in zip(idx, r):
             recs.append((int(i), lab, float(rv)))
     return pd.DataFrame(recs, columns=["row", col, "response"])
@@ -198,8 +338,20 @@ def h_statistic(model, frame: H2OFrame, variables, max_rows=200, seed=0):
     pts = {v: sub.vec(v).data.clone() for v in variables}
     m = sub.nlocal
 
+    fg = _ForestGrid(model, sub)
+    model._pd_why = fg.why_not(variables)
+
     def pd_at(vs):
         out = np.zeros(m)
+        if model._pd_why is None:
+            # one primitive call: the grid is the m sampled points' own (adapted) values
+            # of the columns vs, the rows are the m sampled rows; ceil(m / 64) chunks
+            names = fg.names()
+            grid = fg.X()[[names.index(v) for v in vs]].clone()
+            for g0, r0, (r,) in fg.responses(vs, grid):
+                out[g0:g0 + r.shape[0]] += r.sum(1).cpu().numpy()
+            out /= max(m, 1)
+            return out - out.mean()
         for i in range(m):
             f = sub
             for v in vs:

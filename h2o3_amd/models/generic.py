@@ -280,9 +280,12 @@ class H2OGenericEstimator(H2OEstimator):
         return torch.stack(cols, 0).contiguous() if cols else torch.zeros((0, n), device=cloud.device())
 
     def _forest_raw(self, frame):
-        X = self._score_matrix(frame)
+        return self._raw_from_sums(self._forest.predict(self._score_matrix(frame), self._K))
+
+    def _raw_from_sums(self, sums):
+        """Raw predictions from Forest.predict's [n, K] sums (device forest)."""
         K = self._K
-        s = self._forest.predict(X, K).to(torch.float64)
+        s = sums.to(torch.float64)
         algo = self._mojo.algo
         if algo in ("gbm", "xgboost"):
             f = s + torch.tensor(self._init_f, dtype=torch.float64, device=s.device).view(1, -1)

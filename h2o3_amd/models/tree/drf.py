@@ -157,8 +157,11 @@ class H2ORandomForestEstimator(SharedTreeEstimator):
     def _predict_raw(self, frame):
         X = self._score_matrix(frame)
         K = self._K
-        sums = self._forest.predict(X, K)
-        ntrees = max(1, len(self._forest) // K)
+        return self._raw_from_sums(self._forest.predict(X, K))
+
+    def _raw_from_sums(self, sums):
+        """Raw predictions from Forest.predict's [n, K] sums."""
+        ntrees = max(1, len(self._forest) // self._K)
         return self._normalize(sums / ntrees)
 
     def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None,

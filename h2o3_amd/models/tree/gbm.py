@@ -759,7 +759,14 @@ class H2OGradientBoostingEstimator(SharedTreeEstimator):
         return f
 
     def _predict_raw(self, frame):
-        f = self._predict_link(frame)
+        return self._raw_from_link(self._predict_link(frame))
+
+    def _raw_from_sums(self, sums):
+        """Raw predictions from Forest.predict's [n, K] sums (no offset column)."""
+        return self._raw_from_link(sums + torch.tensor(self._init_f, dtype=torch.float32,
+                                                       device=sums.device).view(1, -1))
+
+    def _raw_from_link(self, f):
         if self._K > 1:
             return torch.softmax(f, 1)
         mu = self._dist.linkinv(f[:, 0])

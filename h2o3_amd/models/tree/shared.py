@@ -313,6 +313,14 @@ class Forest:
             return leaf_out if leaf else out
         return self._predict_torch(X, K, P, leaf)
 
+    def predict_grid(self, X: torch.Tensor, K: int, cols, grid: torch.Tensor, upto=None):
+        """X: [F, N] float32 column-major; cols: 1 to 4 feature indices; grid
+        [len(cols), G] float32 (NaN = NA).  Returns [G, N, K] sums: out[g] is
+        bit for bit predict(X', K) for X' = X with row cols[s] set to
+        grid[s, g] for every s (partial dependence; ops/pd_ops.py)."""
+        from ...ops import pd_ops
+        return pd_ops.forest_grid_sums(self.pack(X.device, upto), X, K, cols, grid).sums
+
     @staticmethod
     def _predict_torch(X, K, P, leaf=False):
         N = X.shape[1]

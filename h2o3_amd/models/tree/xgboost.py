@@ -420,15 +420,19 @@ class H2OXGBoostEstimator(SharedTreeEstimator):
         return 777 if s is None or s == -1 else int(s) & 0x7FFFFFFF
 
     def _predict_raw(self, frame):
-        K = self._K
         if getattr(self, "_gblinear", None) is not None:
             W, b = self._gblinear
             Xd = self._gbl_di.expand(frame, pad=False)[0].to(torch.float64)
-            f = (Xd @ W + b.view(1, -1)).to(torch.float32)
-        else:
-            X = self._score_matrix(frame)
-            f = self._forest.predict(X, K) + torch.tensor(self._init_f, dtype=torch.float32,
-                                                          device=X.device).view(1, -1)
+            return self._raw_from_link((Xd @ W + b.view(1, -1)).to(torch.float32))
+        return self._raw_from_sums(self._forest.predict(self._score_matrix(frame), self._K))
+
+    def _raw_from_sums(self, sums):
+        """Raw predictions of a gbtree model from Forest.predict's [n, K] sums."""
+        return self._raw_from_link(sums + torch.tensor(self._init_f, dtype=torch.float32,
+                                                       device=sums.device).view(1, -1))
+
+    def _raw_from_link(self, f):
+        K = self._K
         if K > 1:
             return torch.softmax(f, 1)
         mu = self._dist.linkinv(f[:, 0])

@@ -1082,15 +1082,21 @@ def create_app(flow_dir: str | None = None, serve: bool = True) -> FastAPI:
     @route("POST", "/3/PartialDependence/")
     def partial_dependence(p, r):
         """PartialDependenceHandler: 1-D partial dependence tables per column
-        (per target class when `targets` is given), kept under destination_key."""
+        (per target class when `targets` is given), then one 2-D table per pair
+        of col_pairs_2dpdp ([[col1, col2], ...]), kept under destination_key."""
         m, fr = _model(p.get("model_id")), _frame(p.get("frame_id"))
-        cols = p.get("cols") or [c for c in (m._spec.x if m._spec is not None else [])]
+        pairs = p.get("col_pairs_2dpdp") or []
+        if isinstance(pairs, str):
+            pairs = S.parse_value(pairs)
+        pairs = [[str(c) for c in pr] for pr in pairs]
+        cols = p.get("cols") or ([] if pairs else [c for c in (m._spec.x if m._spec is not None else [])])
         w = p.get("weight_column_index")
         wname = fr.names[int(w)] if isinstance(w, int) and w >= 0 else None
         row = p.get("row_index")
         tabs = m.partial_plot(fr, cols=list(cols), nbins=int(p.get("nbins", 20)), weight_column=wname,
                               include_na=bool(p.get("add_missing_na", False)), targets=p.get("targets"),
-                              row_index=None if row is None or int(row) < 0 else int(row))
+                              row_index=None if row is None or int(row) < 0 else int(row),
+                              col_pairs_2dpdp=pairs or None)
         dest = p.get("destination_key") or f"pdp_{spmd.rand_hex(8)}"
         pdp[dest] = {"model_id": m.model_id, "frame_id": fr.frame_id, "tables": tabs}
         return S.job_v3(key_name=f"pdp_{dest}", dest=dest, description="PartialDependencePlot")
@@ -1105,7 +1111,8 @@ def create_app(flow_dir: str | None = None, serve: bool = True) -> FastAPI:
         tabs = []
         for t in rec["tables"]:
             df = t if hasattr(t, "columns") else t.as_data_frame()
-            tabs.append(S.twodim_from_df(f"PartialDependence for {df.columns[0]}", df))
+            what = df.columns[0] if df.columns[1] == "mean_response" else f"{df.columns[0]} and {df.columns[1]}"
+            tabs.append(S.twodim_from_df(f"PartialDependence for {what}", df))
         return {"__meta": S.meta("PartialDependenceV3", "PartialDependence"), "model_id": S.key(rec["model_id"], "Model"),
                 "frame_id": S.key(rec["frame_id"]), "destination_key": S.key(dest), "partial_dependence_data": tabs}
 
