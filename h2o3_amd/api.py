@@ -317,6 +317,20 @@ pd_multi_plot = _xp("pd_multi_plot")
 varimp = _xp("varimp")
 
 
+def disparate_analysis(models, frame, protected_columns, reference, favorable_class, air_metric="selectedRatio",
+                       alpha=0.05):
+    """h2o.explanation.disparate_analysis: one row of adverse-impact statistics
+    per binomial model (models/fairness.py)."""
+    from .models.fairness import disparate_analysis as _da
+    return _da(models, frame, protected_columns, reference, favorable_class, air_metric=air_metric, alpha=alpha)
+
+
+def inspect_model_fairness(model, frame, protected_columns, reference, favorable_class, columns=None):
+    """The tables of the reference's fairness report (models/fairness.py)."""
+    from .models.fairness import inspect_model_fairness as _imf
+    return _imf(model, frame, protected_columns, reference, favorable_class, columns=columns)
+
+
 def permutation_importance(model, frame, metric="AUTO", n_samples=10000, n_repeats=1, features=None, seed=-1,
                            use_pandas=True):
     return model.permutation_importance(frame, metric, n_samples, n_repeats, features, seed)

@@ -14,6 +14,8 @@ import contextlib
 import numpy as np
 
 from .models.explain import h_statistic, ice, partial_dependence, permutation_importance  # noqa: F401
+from .models.fairness import (disparate_analysis, fair_pd, fair_shap, fairness_metrics,  # noqa: F401
+                              inspect_model_fairness)
 from .models.explain_plots import (ice_plot, learning_curve_plot, model_correlation,  # noqa: F401
                                    model_correlation_heatmap, pd_multi_plot, pd_plot, residual_analysis_plot,
                                    shap_explain_row_plot, shap_summary_plot, varimp, varimp_heatmap)
@@ -21,7 +23,8 @@ from .models.explain_plots import (ice_plot, learning_curve_plot, model_correlat
 __all__ = ["explain", "explain_row", "varimp_heatmap", "model_correlation_heatmap", "pd_multi_plot", "varimp",
            "model_correlation", "pareto_front", "shap_summary_plot", "shap_explain_row_plot", "pd_plot", "ice_plot",
            "pd_ice_common", "residual_analysis_plot", "learning_curve_plot", "no_progress",
-           "register_explain_methods"]
+           "register_explain_methods", "disparate_analysis", "inspect_model_fairness", "fairness_metrics", "fair_pd",
+           "fair_shap"]
 
 
 def explain(models, frame, columns=None, top_n_features=5, include_explanations="ALL", exclude_explanations=(),

@@ -1251,6 +1251,17 @@ class H2OEstimator:
                                   include_na=include_na, user_splits=user_splits, targets=targets,
                                   row_index=row_index, col_pairs_2dpdp=col_pairs_2dpdp)
 
+    def fairness_metrics(self, frame, protected_columns, reference, favorable_class):
+        """Per intersection of the protected columns: confusion matrix, AUC,
+        logloss, adverse impact ratios against `reference` and the p.value of
+        the selection rates (models/fairness.py)."""
+        from .fairness import fairness_metrics
+        return fairness_metrics(self, frame, protected_columns, reference, favorable_class)
+
+    def inspect_model_fairness(self, frame, protected_columns, reference, favorable_class, columns=None):
+        from .fairness import inspect_model_fairness
+        return inspect_model_fairness(self, frame, protected_columns, reference, favorable_class, columns=columns)
+
     def permutation_importance(self, frame, metric="AUTO", n_samples=10000, n_repeats=1, features=None, seed=-1,
                                use_pandas=True):
         from .explain import permutation_importance
