@@ -45,14 +45,13 @@ no adaptive histogram types, max_depth <= 11.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 
 import numpy as np
 import torch
 
-from ...ops import tree_ops
-from ...ops.tree_ops import _ptr, _stream
+from ...ops import _native, tree_ops
+from ...ops._native import check as _ck, ptr as _ptr, stream as _stream
 from ...parallel import cloud
 from ...parallel import collectives as coll
 from ...utils import graphs
@@ -61,46 +60,10 @@ from .engine import _TreeBuf
 RS = 16
 (GAIN, FEAT, T, OPT, L0, L1, R0, R1, T0, T1, OK, NL, NAW, ST, CT, VAL) = range(16)
 MAX_DEPTH = 11
-_cv, _ci, _cll, _cd, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, ctypes.c_float
 
 
 def _libs():
-    from ...ops import _native
-    lh = tree_ops._lib()
-    ls = _native.get_lib("tree_split")
-    if not getattr(lh, "_typed_dt", False):
-        lh.h2o_dt_items.argtypes = [_ci, _cv, _ci, _ci, _ci, _ci, _ci, _cv, _cv, _cv, _cv]
-        lh.h2o_dt_offsets.argtypes = [_cv, _cv, _cv, _cv, _ci, _cv, _cv, _cv, _cv]
-        lh.h2o_dt_sibling.argtypes = [_cv, _cv, _cv, _ci, _ci, _ci, _ci, _ci, _ci, _cv, _cv, _cv, _cv, _cv]
-        lh.h2o_dt_leaf_vals.argtypes = [_cv, _cv, _ci, _ci, _cv, _cd, _cv, _cv]
-        lh.h2o_dt_root.argtypes = [_cv, _cll, _cv]
-        lh.h2o_part_flags_dev.argtypes = [_cv, _ci, _cll, _cll, _cv, _cv, _cv, _ci, _cv, _cv, _ci, _cv, _cv, _cv, _cv]
-        lh.h2o_part_compact_dev.argtypes = [_cv, _cv, _cv, _ci, _cv, _cv, _cv, _cv, _cv, _cv, _cv, _cv]
-        lh.h2o_leaf_pos_dev.argtypes = [_cv, _cv, _ci, _ci, _cv, _cv, _cv]
-        lh.h2o_leaf_scatter_dev.argtypes = [_cv, _cv, _ci, _cv, _cv, _cv, _cv]
-        lh.h2o_hist_bm.argtypes = [_cv, _ci, _cv, _cv, _cv, _cv, _ci, _ci, _ci, _ci, _cf, _cf, _cv, _ci, _ci, _cv,
-                                   _ci, _cll, _ci, _cv, _cv, _cv, _cv]
-        lh.h2o_gbm_grad.argtypes = [_cv, _cv, _cv, _ci, _cll, _cv, _cv, _cv]
-        lh.h2o_iota_i32.argtypes = [_cv, _cll, _cv]
-        lh.h2o_dt_root_leaf_iota.argtypes = [_cv, _cv, _cll, _cv]
-        lh.h2o_dt_colmask.argtypes = [_ci, _cv, _cv, _cv, _cv, _cv, _ci, _ci, _cv, _cv]
-        lh.h2o_dt_items2.argtypes = [_ci, _cv, _ci, _ci, _ci, _ci, _ci, _cv, _cv, _cv, _cv, _cv]
-        lh.h2o_leaf_flag_sums_dev.argtypes = [_cv, _cv, _cv, _ci, _cv, _cv, _ci, _ci, _cv, _cv, _cv]
-        lh.h2o_leaf_gather_lds.argtypes = [_ci, _ci]
-        lh.h2o_leaf_gather_items.argtypes = [_cll, _ci]
-        lh.h2o_leaf_gather_dev.argtypes = [_cv, _ci, _ci, _ci, _cv, _cv, _cv, _cv, _cll, _ci, _ci, _cv, _cv, _cv, _cv,
-                                           _cv, _cv]
-        lh._typed_dt = True
-    if not getattr(ls, "_typed_dt", False):
-        ls.h2o_split_find_b.argtypes = [_cv, _ci, _ci, _ci, _cv, _cv, _cv] + [_cd] * 5 + [_ci, _cv, _cv, _ci, _cv]
-        ls.h2o_split_select2.argtypes = [_cv, _cv, _ci, _ci, _ci, _ci, _cd, _ci, _cv, _cv, _cv, _cv]
-        ls._typed_dt = True
-    return lh, ls
-
-
-def _ck(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: error {rc}")
+    return tree_ops._lib(), _native.get_lib("tree_split")
 
 
 def supported(drv) -> str | None:
@@ -127,7 +90,7 @@ def supported(drv) -> str | None:
         return "mtries"
     if gp.max_leaves:
         return "max_leaves"
-    if tree_ops.bm_groups(bd.F, bd.Fp, bd.Bs, True) is None:
+    if tree_ops.hist_plan(bd, 0, True, bd.nrows_local, grouped=True).kernel != "bm":
         return "histogram layout"
     if drv.offset is not None or getattr(drv.dist, "huber_delta", None) is not None:
         return "offset"
@@ -202,14 +165,16 @@ class DevTreeGBM:
         # leaf values are read through ridx[0], which stays iota.  The
         # histogram kernel has id-free instances for the packed G = 64 layout
         # with 8 codes per lane (the default).
-        n_fg, G = tree_ops.bm_groups(bd.F, bd.Fp, Bs, self.pack)
+        # one plan for the root at N rows, one for the lighter children at half
+        self.plan_r = tree_ops.hist_plan(bd, 0, True, N, grouped=True)
+        self.plan_c = tree_ops.hist_plan(bd, 0, True, (N + 1) // 2, grouped=True)
+        if self.pack and not (self.plan_r.pack and self.plan_c.pack):
+            raise RuntimeError("devtree: histogram chunk too large for the packed path")
+        n_fg, G = self.plan_r.n_fg, self.plan_r.width
         self.n_fg, self.G = n_fg, G
         self.root_ident = D >= 2 and tree_ops.env("H2O3_DEV_ROOT_IDENT", "1") != "0" and self.pack and G == 64 \
             and tree_ops.env("H2O3_HIST_BM_LW", "2") != "1"
-        self.chunk_r = tree_ops.hist_chunk(N, n_fg)
-        self.chunk_c = tree_ops.hist_chunk((N + 1) // 2, n_fg)
-        if self.pack and max(self.chunk_r, self.chunk_c) >= (1 << 23):
-            raise RuntimeError("devtree: histogram chunk too large for the packed path")
+        self.chunk_r, self.chunk_c = self.plan_r.chunk, self.plan_c.chunk
         self.chunk_p = tree_ops._part_chunk(N)
         self.chunk_l = 65536
         # bernoulli residuals with 0/1 weights lie in (-1, 1): static bound;
@@ -247,7 +212,7 @@ class DevTreeGBM:
         self.loff = torch.zeros(self.cap_p, dtype=i32, device=dev)
         self.roff = torch.zeros(self.cap_p, dtype=i32, device=dev)
         self.flags = torch.zeros(N // 64 + self.cap_p + 1, dtype=torch.int64, device=dev)
-        self.part = tree_ops.bm_part(cap_h, n_fg, Bs, G, self.pack, dev)
+        self.part = self.plan_r.part(cap_h, dev)
         self.split_out = torch.zeros(n_lvl_max * max(self.Fl, 1) * 4, dtype=f64, device=dev)
         self.mask = torch.zeros(n_lvl_max * Bs, dtype=torch.uint8, device=dev)
         self.feat_i = torch.zeros(n_lvl_max, dtype=i32, device=dev)
@@ -286,13 +251,8 @@ class DevTreeGBM:
 
     # ---------------------------------------------------------------- scales
     def _scales(self):
-        vm = self.vmax
-        self.s_r = [tree_ops.fixed_point_scale(m, self.chunk_r) for m in vm]
-        self.s_c = [tree_ops.fixed_point_scale(m, self.chunk_c) for m in vm]
-        self.bq_r = self.bq_c = -1
-        if self.pack:
-            self.s_r[1], self.bq_r = tree_ops._pack_scale(vm[1], self.chunk_r)
-            self.s_c[1], self.bq_c = tree_ops._pack_scale(vm[1], self.chunk_c)
+        self.sc_r = self.plan_r.scales(self.vmax)
+        self.sc_c = self.plan_c.scales(self.vmax)
 
     def set_tree_cols(self, mask):
         """Per-tree column sample (col_sample_rate_per_tree): the split kernels'
@@ -349,9 +309,9 @@ class DevTreeGBM:
         off = (1 << d) - 1
         return self.rec[off * RS:]
 
-    def _ridx_ptr(self, d, cur):
-        """Row ids of level d's kernels: null at an id-free root (row id = position)."""
-        return None if (d == 0 and self.root_ident) else _ptr(self.ridx[cur])
+    def _ridx(self, d, cur):
+        """Row ids of level d's kernels: None at an id-free root (row id = position)."""
+        return None if (d == 0 and self.root_ident) else self.ridx[cur]
 
     def _hist(self, d, cur):
         """Level d's histogram [Fl, 2^d, Bs, C] (+ w*y*y [2^d]) into buffer d % 2."""
@@ -367,11 +327,9 @@ class DevTreeGBM:
             nh = bd.F * Bs * C
             buf = self.Hroot
             buf.zero_()
-            tree_ops.set_bm_ragged(lh, self.ragged)
-            _ck(lh.h2o_hist_bm(_ptr(bd.codes), bd.Fp, self._ridx_ptr(0, cur), _ptr(self.pos[cur]), None,
-                               _ptr(self.hwork), self.cap_r, bd.F, 0, Bs, self.s_r[0], self.s_r[1], _ptr(buf), 1, 0,
-                               _ptr(buf[nh:]), 1, self.bq_r, self.G, None, _ptr(self.counts), _ptr(self.part), s),
-                "hist_bm(root)")
+            tree_ops.launch_hist_bm(lh, self.plan_r, bd, self._ridx(0, cur), self.pos[cur], None, self.hwork,
+                                    self.cap_r, self.sc_r, buf, 1, buf[nh:], True, self.part, cnts=self.counts,
+                                    ragged=self.ragged)
             Hl, wl = buf[:nh].view(bd.F, 1, Bs, C), buf[nh:]
             if self.W > 1:
                 Hl, wl = self.drv.grower._rs_hist_wyy(Hl, wl)
@@ -385,10 +343,9 @@ class DevTreeGBM:
         nhb = bd.F * npar * Bs * C
         buf = self.Hb[:nhb + npar]
         buf.zero_()
-        tree_ops.set_bm_ragged(lh, self.ragged)
-        _ck(lh.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(self.ridx[cur]), _ptr(self.pos[cur]), None, _ptr(self.hwork),
-                           self.cap_c, bd.F, 0, Bs, self.s_c[0], self.s_c[1], _ptr(buf), npar, 0, _ptr(buf[nhb:]), 1,
-                           self.bq_c, self.G, None, _ptr(self.counts), _ptr(self.part), s), "hist_bm(child)")
+        tree_ops.launch_hist_bm(lh, self.plan_c, bd, self.ridx[cur], self.pos[cur], None, self.hwork, self.cap_c,
+                                self.sc_c, buf, npar, buf[nhb:], True, self.part, cnts=self.counts,
+                                ragged=self.ragged)
         Hb, wb = buf[:nhb].view(bd.F, npar, Bs, C), buf[nhb:]
         if self.W > 1:
             Hb, wb = self.drv.grower._rs_hist_wyy(Hb, wb)
@@ -442,7 +399,7 @@ class DevTreeGBM:
         _ck(lh.h2o_dt_items2(0, _ptr(recl), n, self.D, 0, self.chunk_p, self.cap_p, _ptr(self.pwork),
                              _ptr(self.fbase), _ptr(self.slot_wb) if skip else None, _ptr(self.counts), s),
             "dt_items(part)")
-        _ck(lh.h2o_part_flags_dev(_ptr(self.pcodes), 1, self.prs, self.pfs, self._ridx_ptr(d, cur),
+        _ck(lh.h2o_part_flags_dev(_ptr(self.pcodes), 1, self.prs, self.pfs, _ptr(self._ridx(d, cur)),
                                   _ptr(self.pwork), _ptr(self.fbase), self.cap_p, _ptr(self.feat_i), _ptr(self.mask),
                                   Bs, _ptr(self.flags), _ptr(self.cnt), _ptr(self.counts), s), "part_flags_dev")
         _ck(lh.h2o_dt_offsets(_ptr(self.cnt), _ptr(self.pwork), _ptr(self.counts), _ptr(recl), n,
@@ -459,7 +416,7 @@ class DevTreeGBM:
         if d == 0 and self.root_ident:
             # a root that stays a leaf is read back through ridx[0] when the depth is odd
             _ck(lh.h2o_dt_root_leaf_iota(_ptr(recl), _ptr(self.ridx[0]), self.N, s), "dt_root_leaf_iota")
-        _ck(lh.h2o_part_compact_dev(self._ridx_ptr(d, cur), _ptr(self.pwork), _ptr(self.fbase), self.cap_p,
+        _ck(lh.h2o_part_compact_dev(_ptr(self._ridx(d, cur)), _ptr(self.pwork), _ptr(self.fbase), self.cap_p,
                                     _ptr(self.flags), _ptr(self.loff), _ptr(self.roff), _ptr(self.ridx[nxt]),
                                     _ptr(self.pos[cur]), _ptr(self.pos[nxt]), _ptr(self.counts), s),
             "part_compact_dev")

@@ -26,7 +26,8 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from ...ops import tree_ops
+from ...ops import _native, tree_ops
+from ...ops._native import check, ptr, stream
 from ...parallel import cloud
 from ...parallel import collectives as coll
 from ...utils.timer import phase
@@ -604,35 +605,21 @@ class TreeGrower:
         ua_fold_kernel): the same first / last, parent-range rule and run-end
         folding as the torch chain of _adapt_hist, one wave per (feature,
         node) row, H read twice and written once."""
-        import ctypes
-        from ...ops import _native
         lib = _native.get_lib("tree_split")
         if lib is None:
             raise RuntimeError("tree_split native library missing (UniformAdaptive fold)")
-        if not getattr(lib, "_typed_ua", False):
-            cv, ci = ctypes.c_void_p, ctypes.c_int
-            lib.h2o_ua_range.argtypes = [cv, ci, ci, ci, cv, cv, cv]
-            lib.h2o_ua_fold.argtypes = [cv, ci, ci, ci, ci, cv, cv, ci, cv, cv, cv]
-            lib._typed_ua = True
         H = H.contiguous()
         rows = Fl * n
         fl = torch.empty(2 * rows, dtype=torch.int32, device=H.device)
-        s = tree_ops._stream()
-        rc = lib.h2o_ua_range(ctypes.c_void_p(H.data_ptr()), rows, Bs, C, ctypes.c_void_p(fl.data_ptr()),
-                              ctypes.c_void_p(fl.data_ptr() + 4 * rows), s)
-        if rc != 0:
-            raise RuntimeError(f"h2o_ua_range failed: {rc}")
+        s = stream()
+        check(lib.h2o_ua_range(ptr(H), rows, Bs, C, ptr(fl), ptr(fl[rows:]), s), "h2o_ua_range")
         first, last = fl[:rows].view(Fl, n, 1).long(), fl[rows:].view(Fl, n, 1).long()
         first, last = self._adapt_range(first, last, n, Fl, depth)
         fr_ = first.to(torch.int32).contiguous()
         la_ = last.to(torch.int32).contiguous()
         isn = isnum.to(torch.uint8).contiguous()
         out = torch.empty_like(H)
-        rc = lib.h2o_ua_fold(ctypes.c_void_p(H.data_ptr()), Fl, n, Bs, C, ctypes.c_void_p(fr_.data_ptr()),
-                             ctypes.c_void_p(la_.data_ptr()), int(nb), ctypes.c_void_p(isn.data_ptr()),
-                             ctypes.c_void_p(out.data_ptr()), s)
-        if rc != 0:
-            raise RuntimeError(f"h2o_ua_fold failed: {rc}")
+        check(lib.h2o_ua_fold(ptr(H), Fl, n, Bs, C, ptr(fr_), ptr(la_), int(nb), ptr(isn), ptr(out), s), "h2o_ua_fold")
         return out
 
     def _adapt_range(self, first, last, n, Fl, depth):
@@ -730,16 +717,9 @@ class TreeGrower:
         return res
 
     def _find_splits_native(self, H, col_mask, node_wyy, want_pk=False):
-        import ctypes
-        from ...ops import _native
         p = self.p
         Fl, n, Bs, C = H.shape
         lib = _native.get_lib("tree_split")
-        if not getattr(lib, "_typed", False):
-            cv = ctypes.c_void_p
-            lib.h2o_split_find.argtypes = [cv, ctypes.c_int, ctypes.c_int, ctypes.c_int, cv, cv, cv] + \
-                [ctypes.c_double] * 5 + [ctypes.c_int, cv, cv]
-            lib._typed = True
         fsl = slice(self.f0, self.f0 + Fl)
         cm = col_mask[:, fsl]
         if getattr(col_mask, "_all_true", False) and self.f0 + Fl <= self.bd.F:
@@ -762,39 +742,21 @@ class TreeGrower:
         out = torch.empty((n * Fl, 4), dtype=torch.float64, device=self.dev)
         crit = 1 if p.criterion == "xgb" else 0
         bnd = self._bnd_dev(n)
-        if not getattr(lib, "_typed_b", False):
-            cv = ctypes.c_void_p
-            lib.h2o_split_find_b.argtypes = [cv, ctypes.c_int, ctypes.c_int, ctypes.c_int, cv, cv, cv] + \
-                [ctypes.c_double] * 5 + [ctypes.c_int, cv, cv, ctypes.c_int, cv]
-            lib._typed_b = True
-        rc = lib.h2o_split_find_b(ctypes.c_void_p(H.data_ptr()), Fl, n, Bs, ctypes.c_void_p(wyy.data_ptr()),
-                                  ctypes.c_void_p(ok.data_ptr()), ctypes.c_void_p(mono.data_ptr()),
-                                  float(p.min_rows), float(p.min_split_improvement), float(p.reg_lambda),
-                                  float(p.reg_alpha), float(p.gamma), crit, ctypes.c_void_p(out.data_ptr()),
-                                  ctypes.c_void_p(0 if bnd is None else bnd.data_ptr()), int(bool(p.use_bounds)),
-                                  tree_ops._stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_split_find failed: {rc}")
+        check(lib.h2o_split_find_b(ptr(H), Fl, n, Bs, ptr(wyy), ptr(ok), ptr(mono), float(p.min_rows),
+                                   float(p.min_split_improvement), float(p.reg_lambda), float(p.reg_alpha),
+                                   float(p.gamma), crit, ptr(out), ptr(bnd), int(bool(p.use_bounds)), stream()),
+              "h2o_split_find_b")
         if C == 2 and want_pk and (self.W > 1 or self.f0 < self.bd.F):
             # selection + split decision + partition inputs in one kernel; the
             # packed record (12 doubles per node) is what the host fetches
-            if not getattr(lib, "_typed_sel2", False):
-                cv = ctypes.c_void_p
-                lib.h2o_split_select2.argtypes = [cv, cv, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                  ctypes.c_double, ctypes.c_int, cv, cv, cv, cv]
-                lib._typed_sel2 = True
             # 13 fields: split_select2's 12 + the node's NA weight on the chosen column
             pk = torch.empty((n, 13), dtype=torch.float64, device=self.dev)
             mask = torch.empty((n, Bs), dtype=torch.uint8, device=self.dev)
             feat_i = torch.empty(n, dtype=torch.int32, device=self.dev)
             if self.f0 < self.bd.F:
                 min_w2 = -1.0 if p.criterion == "xgb" else 2.0 * float(p.min_rows)
-                rc = lib.h2o_split_select2(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(H.data_ptr()), Fl, n,
-                                           Bs, self.f0, min_w2, 13, ctypes.c_void_p(pk.data_ptr()),
-                                           ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(feat_i.data_ptr()),
-                                           tree_ops._stream())
-                if rc != 0:
-                    raise RuntimeError(f"h2o_split_select2 failed: {rc}")
+                check(lib.h2o_split_select2(ptr(out), ptr(H), Fl, n, Bs, self.f0, min_w2, 13, ptr(pk), ptr(mask),
+                                            ptr(feat_i), stream()), "h2o_split_select2")
             else:
                 # a rank holding only padding features: a never-winning record
                 pk.zero_()
@@ -807,18 +769,10 @@ class TreeGrower:
                     "opt": pk[:, 3], "L": pk[:, 4:6], "R": pk[:, 6:8], "tot": pk[:, 8:10]}
         if C == 2 and self.f0 < self.bd.F:
             # fused per-node selection + mask kernel: few launches, one packed record
-            if not getattr(lib, "_typed_sel", False):
-                cv = ctypes.c_void_p
-                lib.h2o_split_select.argtypes = [cv, cv, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, cv,
-                                                 cv, cv]
-                lib._typed_sel = True
             pk = torch.empty((n, 10), dtype=torch.float64, device=self.dev)
             mask = torch.empty((n, Bs), dtype=torch.uint8, device=self.dev)
-            rc = lib.h2o_split_select(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(H.data_ptr()), Fl, n, Bs,
-                                      self.f0, ctypes.c_void_p(pk.data_ptr()), ctypes.c_void_p(mask.data_ptr()),
-                                      tree_ops._stream())
-            if rc != 0:
-                raise RuntimeError(f"h2o_split_select failed: {rc}")
+            check(lib.h2o_split_select(ptr(out), ptr(H), Fl, n, Bs, self.f0, ptr(pk), ptr(mask), stream()),
+                  "h2o_split_select")
             opt = pk[:, 3].long()
             return {"gain": pk[:, 0], "feat": pk[:, 1].long(), "t": pk[:, 2].long(), "opt": opt,
                     "na_left": opt == 1, "mask": mask, "L": pk[:, 4:6], "R": pk[:, 6:8], "tot": pk[:, 8:10]}
@@ -992,8 +946,6 @@ class TreeGrower:
         per-node winner / record / mask (pair_select_kernel) -- the level's
         split record comes out in the packed form of split_select2, so the
         async partition and the single host transfer of the level apply."""
-        import ctypes
-        from ...ops import _native
         p = self.p
         bd, dev = self.bd, self.dev
         Bs = bd.Bs
@@ -1009,10 +961,6 @@ class TreeGrower:
         elif mode == 0 and getattr(self, "_va_eff", None) is not None:
             va, vb = self._va_eff, None
         lib = _native.get_lib("tree_split")
-        if not getattr(lib, "_typed_psel", False):
-            cv, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-            lib.h2o_pair_select.argtypes = [cv, ci, ci, ci, cv, cv, cv, ci, cd, ci, cv, cv, cv, cv]
-            lib._typed_psel = True
         if getattr(self, "_fcat_u8", None) is None:
             self._fcat_u8 = self.is_cat_t[:bd.F].to(torch.uint8).contiguous()
         st = np.asarray(f_st, dtype=np.int64)
@@ -1161,7 +1109,6 @@ class TreeGrower:
         """Score the n*k pairs of Hp (cat_pair_kernel) and write the n nodes'
         records / masks / features (pair_select_kernel) into the given
         contiguous output views."""
-        import ctypes
         p = self.p
         dev = self.dev
         Bs = self.bd.Bs
@@ -1174,24 +1121,14 @@ class TreeGrower:
                                     torch.arange(P, device=dev), self.is_cat_t[fl], self.mono_t[fl],
                                     wyy_n.repeat_interleave(k) if wyy_n is not None else None, raw=True,
                                     pbins=nb_t[fl] if nb_t is not None else None)
+        xgb = 1 if p.criterion == "xgb" else 0
         if nb_t is not None:
-            if not getattr(lib, "_typed_psel2", False):
-                cv, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-                lib.h2o_pair_select2.argtypes = [cv, ci, ci, ci, cv, cv, cv, ci, cd, ci, cv, cv, cv, cv, cv]
-                lib._typed_psel2 = True
-            rc = lib.h2o_pair_select2(ctypes.c_void_p(Hp.data_ptr()), n, Bs, k, ctypes.c_void_p(best_k.data_ptr()),
-                                      ctypes.c_void_p(pfeat.data_ptr()), ctypes.c_void_p(self._fcat_u8.data_ptr()),
-                                      1 if p.criterion == "xgb" else 0, min_w2, pk.stride(0), ctypes.c_void_p(pk.data_ptr()),
-                                      ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(feat_i.data_ptr()),
-                                      ctypes.c_void_p(nb_t.data_ptr()), tree_ops._stream())
+            rc = lib.h2o_pair_select2(ptr(Hp), n, Bs, k, ptr(best_k), ptr(pfeat), ptr(self._fcat_u8), xgb, min_w2,
+                                      pk.stride(0), ptr(pk), ptr(mask), ptr(feat_i), ptr(nb_t), stream())
         else:
-            rc = lib.h2o_pair_select(ctypes.c_void_p(Hp.data_ptr()), n, Bs, k, ctypes.c_void_p(best_k.data_ptr()),
-                                     ctypes.c_void_p(pfeat.data_ptr()), ctypes.c_void_p(self._fcat_u8.data_ptr()),
-                                     1 if p.criterion == "xgb" else 0, min_w2, pk.stride(0), ctypes.c_void_p(pk.data_ptr()),
-                                     ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(feat_i.data_ptr()),
-                                     tree_ops._stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_pair_select failed: {rc}")
+            rc = lib.h2o_pair_select(ptr(Hp), n, Bs, k, ptr(best_k), ptr(pfeat), ptr(self._fcat_u8), xgb, min_w2,
+                                     pk.stride(0), ptr(pk), ptr(mask), ptr(feat_i), stream())
+        check(rc, "h2o_pair_select")
 
     def _pair_direct_part(self, ridx, va, vb, mode, posv, st, ct, pn, pf):
         p = self.p
@@ -1368,15 +1305,9 @@ class TreeGrower:
         """(best gain, k) per pair from the HIP pair kernel.  pbins (bins of each
         pair's feature): pairs of narrow (< 256-bin) features are scored by the
         256-wide kernel instance, the rest at the full histogram width."""
-        import ctypes
-        from ...ops import _native
         p = self.p
         Fl, n, Bs, C = H.shape
         lib = _native.get_lib("tree_split")
-        if not getattr(lib, "_typed_pairs", False):
-            cv, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-            lib.h2o_cat_pairs.argtypes = [cv, ci, ci, ci, ci, cv, cv, cv, cv, cv, cd, cd, cd, cd, cd, ci, cv, cv]
-            lib._typed_pairs = True
         H = H.contiguous()
         P = fslot.numel()
         pf = fslot.to(torch.int32).contiguous()
@@ -1385,30 +1316,20 @@ class TreeGrower:
         pm = mono_p.to(torch.float32).contiguous()
         wyy = node_wyy.to(torch.float64).contiguous() if node_wyy is not None else None
         res = torch.empty((P, 2), dtype=torch.float64, device=H.device)
-
-        def ptr(t):
-            return ctypes.c_void_p(0 if t is None else t.data_ptr())
         if pbins is not None and Bs - 1 > 256 and tree_ops.env("H2O3_PAIR_NARROW", "1") == "1":
-            if not getattr(lib, "_typed_pairs2", False):
-                cv, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-                lib.h2o_cat_pairs2.argtypes = [cv, ci, ci, ci, ci, cv, cv, cv, cv, cv, cd, cd, cd, cd, cd, ci, cv,
-                                               cv, ci, cv, cv]
-                lib._typed_pairs2 = True
             lists = torch.empty(2 * P + 2, dtype=torch.int32, device=H.device)
             pb = pbins.to(torch.int32).contiguous()
             rc = lib.h2o_cat_pairs2(ptr(H), n, Bs, C, P, ptr(pf), ptr(pn), ptr(pc), ptr(pm), ptr(wyy),
                                     float(p.min_rows), float(p.min_split_improvement), float(p.reg_lambda),
                                     float(p.reg_alpha), float(p.gamma), 1 if p.criterion == "xgb" else 0, ptr(res),
-                                    ptr(pb), 255, ptr(lists), tree_ops._stream())
-            if rc != 0:
-                raise RuntimeError(f"h2o_cat_pairs2 failed: {rc}")
+                                    ptr(pb), 255, ptr(lists), stream())
+            check(rc, "h2o_cat_pairs2")
             return res if raw else (res[:, 0].contiguous(), res[:, 1].to(torch.long))
         rc = lib.h2o_cat_pairs(ptr(H), n, Bs, C, P, ptr(pf), ptr(pn), ptr(pc), ptr(pm), ptr(wyy),
                                float(p.min_rows), float(p.min_split_improvement), float(p.reg_lambda),
                                float(p.reg_alpha), float(p.gamma), 1 if p.criterion == "xgb" else 0, ptr(res),
-                               tree_ops._stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_cat_pairs failed: {rc}")
+                               stream())
+        check(rc, "h2o_cat_pairs")
         if raw:
             return res
         return res[:, 0].contiguous(), res[:, 1].to(torch.long)

@@ -7,7 +7,6 @@ hex/tree/CompressedForest.java.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
@@ -17,17 +16,11 @@ import torch
 from ...core.frame import H2OFrame
 from ...core.vec import T_ENUM, T_INT, T_REAL, Vec
 from ...ops import _native
+from ...ops._native import check as _check, ptr as _ptr, stream as _stream
 from ...parallel import cloud
 from ..base import H2OEstimator
 from .binning import bin_frame_tensors
 from .engine import Tree
-
-_c_void = ctypes.c_void_p
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
 
 def iter_seed(seed, it, salt=0):
     """Seed of boosting / forest iteration `it`: every tree's randomness
@@ -297,19 +290,12 @@ class Forest:
             return leaf_out if leaf else out
         if X.device.type == "cuda":
             lib = _native.get_lib("tree_predict")
-            if not getattr(lib, "_typed2", False):
-                lib.h2o_forest_predict.argtypes = [_c_void, ctypes.c_longlong] + [_c_void] * 7 + \
-                    [ctypes.c_int, ctypes.c_int, _c_void, _c_void, _c_void]
-                lib._typed2 = True
             X = X.contiguous().to(torch.float32)
             rc = lib.h2o_forest_predict(_ptr(X), N, _ptr(P["node"]), _ptr(P["cat_off"]),
                                         _ptr(P["cat_len"]), _ptr(P["cat_bits"]), _ptr(P["value"]),
                                         _ptr(P["roots"]), _ptr(P["tclass"]), T, K,
-                                        _ptr(out) if not leaf else ctypes.c_void_p(0),
-                                        _ptr(leaf_out) if leaf else ctypes.c_void_p(0),
-                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"h2o_forest_predict failed: {rc}")
+                                        _ptr(None if leaf else out), _ptr(leaf_out if leaf else None), _stream())
+            _check(rc, "h2o_forest_predict")
             return leaf_out if leaf else out
         return self._predict_torch(X, K, P, leaf)
 

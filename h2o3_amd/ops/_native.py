@@ -20,6 +20,10 @@ import os
 import subprocess
 import threading
 
+import torch
+
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
@@ -112,11 +116,7 @@ def build_all(force: bool = False, verbose: bool = False, jobs: int = 8) -> list
 
 
 def gpu_present() -> bool:
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:  # pragma: no cover
-        return False
+    return torch.cuda.is_available()
 
 
 def get_lib(name: str, required: bool | None = None):
@@ -142,8 +142,32 @@ def get_lib(name: str, required: bool | None = None):
                 raise RuntimeError(f"native library {p} missing: run __graft_entry__.build()")
             return None
         lib = ctypes.CDLL(p)
+        _abi.apply(name, lib)      # argtypes / restype of every h2o_* export, once
         _libs[name] = lib
         return lib
+
+
+def ptr(t):
+    """Data pointer of a tensor for a `P` argument; null for None."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+_get_device = getattr(torch._C, "_cuda_getDevice", None)
+
+
+def stream():
+    """Current HIP stream as a ctypes pointer (the raw C getters: ~10x cheaper
+    than torch.cuda.current_stream(), called for every kernel launch)."""
+    if _raw_stream is not None and _get_device is not None:
+        return ctypes.c_void_p(_raw_stream(_get_device()))
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def check(rc, what):
+    """Raise unless a launch wrapper returned 0 (`what`: function name, context)."""
+    if rc != 0:
+        raise RuntimeError(f"{what} failed: error {rc}")
 
 
 def loaded_libs() -> list[str]:

@@ -11,31 +11,15 @@ whose assignment changed.  Reference: hex/kmeans/KMeans.java:731
 """
 from __future__ import annotations
 
-import ctypes
 import torch
 
 from . import _native
+from ._native import check as _check, ptr as _ptr, stream as _stream
 
-_cv, _ci, _cll, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 
 
 def _lib():
-    lib = _native.get_lib("kmeans")
-    if lib is not None and not getattr(lib, "_typed", False):
-        lib.h2o_kmeans_lloyd.argtypes = [_cv, _cv, _cll, _ci, _cv, _cv, _ci, _cv, _cv, _cv, _cv, _ci, _ci, _cf, _cv]
-        lib.h2o_kmeans_reduce.argtypes = [_cv, _ci, _cll, _cv, _cv]
-        lib.h2o_kmeans_max_k.argtypes = [_ci, _ci]
-        lib.h2o_kmeans_part_stride.argtypes = [_ci, _ci]
-        lib.h2o_kmeans_part_stride.restype = _cll
-        lib.h2o_kmeans_resident_per_cu.argtypes = [_ci, _ci, _ci, _cf]
-        lib.h2o_kmeans_sums.argtypes = [_cv, _cv, _cll, _ci, _ci, _cv, _cv, _cv, _cv, _ci, _cf, _cv]
-        lib.h2o_kmeans_sums_resident_per_cu.argtypes = [_ci, _ci]
-        lib.h2o_kmeans_assign.argtypes = [_cv, _cll, _ci, _cv, _cv, _ci, _cv, _cv, _ci, _cv]
-        lib.h2o_kmeans_assign_resident_per_cu.argtypes = [_ci, _ci]
-        lib.h2o_xv.argtypes = [_cv, _cll, _ci, _cv, _ci, _cv, _ci, _cv]
-        lib.h2o_xv_resident_per_cu.argtypes = [_ci, _ci]
-        lib._typed = True
-    return lib
+    return _native.get_lib("kmeans")
 
 
 _CU = {}
@@ -45,10 +29,6 @@ def _cu_count(dev):
     if dev not in _CU:
         _CU[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
     return _CU[dev]
-
-
-def _ptr(t):
-    return _cv(0 if t is None else t.data_ptr())
 
 
 class LloydStats:
@@ -121,7 +101,7 @@ def lloyd_pass(X, C, w=None, assign=None, accumulate=True, dmin=None, use_native
         fx = float(2.0 ** 62 / (max(xabs_max, 1e-30) * rows_wg)) if xabs_max > 0 else 1.0
         fx = min(fx, 2.0 ** 100)
     stride = int(lib.h2o_kmeans_part_stride(k, P))
-    stream = _cv(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
     if accumulate and fx > 0 and n_groups is None and _split_ok(lib, k, P, fx):
         return _lloyd_split(lib, X, C32, cn, wt, k, P, ntiles, assign, dmin, xabs_max, stride, stream)
     if n_groups is None:
@@ -133,14 +113,12 @@ def lloyd_pass(X, C, w=None, assign=None, accumulate=True, dmin=None, use_native
         part = torch.empty((n_groups, stride), dtype=torch.float64, device=X.device)
     rc = lib.h2o_kmeans_lloyd(_ptr(X), _ptr(wt), N, P, _ptr(C32), _ptr(cn), k, _ptr(assign), _ptr(assign), _ptr(dmin),
                               _ptr(part), n_groups, 1 if accumulate else 0, fx, stream)
-    if rc != 0:
-        raise RuntimeError(f"h2o_kmeans_lloyd failed: {rc}")
+    _check(rc, "h2o_kmeans_lloyd")
     if not accumulate:
         return None
     out = torch.empty(stride, dtype=torch.float64, device=X.device)
     rc = lib.h2o_kmeans_reduce(_ptr(part), n_groups, stride, _ptr(out), stream)
-    if rc != 0:
-        raise RuntimeError(f"h2o_kmeans_reduce failed: {rc}")
+    _check(rc, "h2o_kmeans_reduce")
     return LloydStats(out, k, P)
 
 
@@ -177,15 +155,13 @@ def _lloyd_split(lib, X, C32, cn, wt, k, P, ntiles, assign, dmin, xabs_max, stri
         # centers in LDS (kmeans_assign_kernel)
         g1 = max(1, min(-(-N // 64), per_cu * cus))
         rc = lib.h2o_kmeans_assign(_ptr(X), N, P, _ptr(C32), _ptr(cn), k, _ptr(asg_new), _ptr(d2), g1, stream)
-        if rc != 0:
-            raise RuntimeError(f"h2o_kmeans_assign failed: {rc}")
+        _check(rc, "h2o_kmeans_assign")
     else:
         per_cu = int(lib.h2o_kmeans_resident_per_cu(k, P, 0, 0.0))
         g1 = max(1, min(ntiles, max(per_cu, 1) * cus))
         rc = lib.h2o_kmeans_lloyd(_ptr(X), _ptr(wt), N, P, _ptr(C32), _ptr(cn), k, _ptr(asg_new), None, _ptr(d2),
                                   None, g1, 0, 0.0, stream)
-        if rc != 0:
-            raise RuntimeError(f"h2o_kmeans_lloyd (assignment pass) failed: {rc}")
+        _check(rc, "h2o_kmeans_lloyd (assignment pass)")
     g2 = max(1, min(ntiles, max(int(lib.h2o_kmeans_sums_resident_per_cu(k, P)), 1) * cus))
     rows_wg = 64 * (-(-ntiles // g2))
     fx = float(2.0 ** 62 / (max(xabs_max, 1e-30) * rows_wg)) if xabs_max > 0 else 1.0
@@ -193,12 +169,10 @@ def _lloyd_split(lib, X, C32, cn, wt, k, P, ntiles, assign, dmin, xabs_max, stri
     part = torch.empty((g2, stride), dtype=torch.float64, device=dev)
     rc = lib.h2o_kmeans_sums(_ptr(X), _ptr(wt), N, P, k, _ptr(asg_new), _ptr(assign), _ptr(d2), _ptr(part), g2, fx,
                              stream)
-    if rc != 0:
-        raise RuntimeError(f"h2o_kmeans_sums failed: {rc}")
+    _check(rc, "h2o_kmeans_sums")
     out = torch.empty(stride, dtype=torch.float64, device=dev)
     rc = lib.h2o_kmeans_reduce(_ptr(part), g2, stride, _ptr(out), stream)
-    if rc != 0:
-        raise RuntimeError(f"h2o_kmeans_reduce failed: {rc}")
+    _check(rc, "h2o_kmeans_reduce")
     if assign is not None:
         assign.copy_(asg_new)
     if dmin is not None and d2 is not dmin:
@@ -260,7 +234,6 @@ def xv(X, V, min_rows=None):
     if per_cu < 1:
         return X.to(torch.float64) @ V.to(device=X.device, dtype=torch.float64)
     G = max(1, min(-(-N // 64), per_cu * _cu_count(X.device)))
-    rc = lib.h2o_xv(_ptr(Xc), N, W, _ptr(Vt), k, _ptr(out), G, _cv(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"h2o_xv failed: {rc}")
+    rc = lib.h2o_xv(_ptr(Xc), N, W, _ptr(Vt), k, _ptr(out), G, _stream())
+    _check(rc, "h2o_xv")
     return out

@@ -19,44 +19,18 @@ import ctypes
 import torch
 
 from . import _native
+from ._native import check as _check, ptr as _p, stream as _s
 
 ACT = {"linear": 0, "tanh": 1, "rectifier": 2, "exprectifier": 3, "maxout": 4}
-_cv, _ci, _cf, _cull = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
+_cv, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
 
 def _lib():
-    lib = _native.get_lib("dl")
-    if lib is not None and not getattr(lib, "_typed", False):
-        lib.h2o_dl_fwd.argtypes = [_cv, _cv, _cv, _ci, _ci, _ci, _cf, _cull, _cv, _ci, _cf, _cv]
-        lib.h2o_dl_bwd.argtypes = [_cv, _cv, _cv, _cv, _cv, _ci, _ci, _ci, _cf, _cull, _cv, _cv]
-        lib.h2o_dl_seed_advance.argtypes = [_cv, _cv]
-        lib.h2o_dl_update.argtypes = [_cv] * 9 + [_ci, _ci] + [_cf] * 7 + [_ci] * 3 + [_cf, _cf, _cv]
-        lib.h2o_dl_softmax.argtypes = [_cv] * 7 + [_ci, _ci, _cf, _ci, _cv]
-        lib.h2o_dl_mlp_step.argtypes = [_ci] + [_cv] * 15 + [_ci] + [_cv] * 4 + [_ci, _ci, _cf, _cull, _cv, _ci,
-                                                                            _cv]
-        lib.h2o_dl_gemm.argtypes = [_ci, _ci, _ci, _cv, ctypes.c_longlong, ctypes.c_longlong, _cv,
-                                    ctypes.c_longlong, ctypes.c_longlong, _cv, _cv, ctypes.c_longlong, _cv]
-        lib.h2o_dl_gemm_ws.argtypes = [_ci, _ci, _ci]
-        lib.h2o_dl_gemm_ws.restype = ctypes.c_longlong
-        lib._typed = True
-    return lib
-
-
-def _p(t):
-    return _cv(0 if t is None else t.data_ptr())
-
-
-def _s():
-    return _cv(torch.cuda.current_stream().cuda_stream)
+    return _native.get_lib("dl")
 
 
 def _native_ok(t, use_native):
     return (t.device.type == "cuda") if use_native is None else use_native
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed: {rc}")
 
 
 # ---------------------------------------------------------------- dropout hash

@@ -27,6 +27,7 @@ import ctypes
 import torch
 
 from . import _native, dl_ops
+from ._native import check, ptr as _ptr, stream as _stream
 from .shap_ops import ShapResult
 
 EPS = 1e-6                      # |a(x) - a(z)| below which the derivative is used
@@ -38,7 +39,7 @@ _ROW_TILE_CAP = 1 << 19
 # faster than the torch rule at both shapes of profiles/dl_shap_mb.txt
 # (10k x 100: 2.4x, 1 x 10k: 1.2x)
 NATIVE_DEFAULT = True
-_cv, _ci, _cll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+_cv, _ci = ctypes.c_void_p, ctypes.c_int
 
 
 class DeepShapResult(ShapResult):
@@ -177,14 +178,7 @@ def deep_shap_torch(layers, acts, scales, out_w, X, Z, per_reference=False, pair
 
 # ------------------------------------------------------------------ kernel
 def _lib():
-    lib = _native.get_lib("dl_shap", required=True)
-    if not getattr(lib, "_typed", False):
-        lib.h2o_dl_shap_chunk.restype = _ci
-        lib.h2o_dl_shap_lds.argtypes = [_ci, _cv]
-        lib.h2o_dl_shap_lds.restype = _cll
-        lib.h2o_dl_shap_pairs.argtypes = [_ci] + [_cv] * 10 + [_ci, _ci, _cv, _cv, _cll, _cll, _cll, _ci, _ci, _cv]
-        lib._typed = True
-    return lib
+    return _native.get_lib("dl_shap", required=True)
 
 
 def dl_shap_lds_bytes(widths) -> int:
@@ -287,7 +281,7 @@ def deep_shap(layers, acts, scales, out_w, X, Z, per_reference=False, pair_scale
     actc = (_ci * nl)(*[dl_ops.ACT[a] for a in acts])
     scc = (ctypes.c_float * nl)(*[float(s) for s in scales])
     Wp = (_cv * nl)(*[W.data_ptr() for W, _ in layers])
-    stream = _cv(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
     ev = None
     if timing is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -307,12 +301,10 @@ def deep_shap(layers, acts, scales, out_w, X, Z, per_reference=False, pair_scale
                 assert S.shape == (nr, nb)
             pzp = (_cv * nl)(*[p.data_ptr() + 4 * b0 * p.shape[1] for p in pre_z])
             rc = lib.h2o_dl_shap_pairs(nl, wid, actc, scc, Wp, pxp, pzp, _cv(X.data_ptr() + 4 * r0 * P),
-                                       _cv(Z.data_ptr() + 4 * b0 * P), _cv(out_w.data_ptr()),
-                                       _cv(0 if S is None else S.data_ptr()), nr, nb,
-                                       _cv(0 if partial is None else partial.data_ptr()), _cv(phi.data_ptr()),
-                                       r0, b0, B, 1 if per_reference else 0, 1 if swap else 0, stream)
-            if rc != 0:
-                raise RuntimeError(f"h2o_dl_shap_pairs failed: {rc}")
+                                       _cv(Z.data_ptr() + 4 * b0 * P), _ptr(out_w), _ptr(S), nr, nb,
+                                       _ptr(partial), _ptr(phi), r0, b0, B, 1 if per_reference else 0,
+                                       1 if swap else 0, stream)
+            check(rc, "h2o_dl_shap_pairs")
     if ev is not None:
         ev[1].record()
         torch.cuda.synchronize()

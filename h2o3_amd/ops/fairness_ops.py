@@ -25,10 +25,10 @@ import ctypes
 import torch
 
 from . import _native
+from ._native import check, ptr as _ptr, stream as _stream
 
 LDS_GROUPS = 512              # groups whose per-group cells accumulate in LDS (FS_LDS_GROUPS of the kernel)
 _c_void = ctypes.c_void_p
-_c_int = ctypes.c_int
 
 
 class SketchResult:
@@ -47,14 +47,10 @@ class SketchResult:
         self.cnt, self.cm, self.sums, self.kernel, self.why, self.chunks = cnt, cm, sums, kernel, why, chunks
 
 
-def _typed(lib):
-    if not getattr(lib, "_typed", False):
-        lib.h2o_group_sketch.argtypes = [_c_void, _c_int, _c_void, _c_void, ctypes.c_longlong, _c_int, _c_int, _c_int,
-                                         ctypes.c_double, _c_int, _c_void, _c_void, _c_void, _c_int, _c_void]
-        lib.h2o_fairness_lds_groups.argtypes = []
-        if lib.h2o_fairness_lds_groups() != LDS_GROUPS:
-            raise RuntimeError("libfairness.so was built with another LDS_GROUPS than fairness_ops.py states")
-        lib._typed = True
+def _lib():
+    lib = _native.get_lib("fairness", required=True)
+    if lib.h2o_fairness_lds_groups() != LDS_GROUPS:
+        raise RuntimeError("libfairness.so was built with another LDS_GROUPS than fairness_ops.py states")
     return lib
 
 
@@ -140,7 +136,7 @@ def group_sketch(p1, y, g, G, thr, flip=False, nb=1 << 18, max_bytes=1 << 30, ma
     n = p1.numel()
     if n == 0 or G == 0:
         return SketchResult(cnt, cm, sums, True, None, 0)
-    lib = _typed(_native.get_lib("fairness", required=True))
+    lib = _lib()
     p1 = p1.contiguous()
     # wider codes are narrowed after the filter, so none wraps into range
     if y.dtype != torch.int32:
@@ -150,16 +146,14 @@ def group_sketch(p1, y, g, G, thr, flip=False, nb=1 << 18, max_bytes=1 << 30, ma
     y = y.to(device=dev, dtype=torch.int32).contiguous()
     g = g.to(device=dev, dtype=torch.int32).contiguous()
     per = max(1, int(max_bytes) // (2 * nb * 8))
-    stream = _c_void(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
     chunks = 0
     for g0 in range(0, G, per):
         gc = min(per, G - g0)
-        rc = lib.h2o_group_sketch(_c_void(p1.data_ptr()), 1 if p1.dtype == torch.float64 else 0,
-                                  _c_void(y.data_ptr()), _c_void(g.data_ptr()), n, nb, g0, gc, float(thr),
-                                  1 if flip else 0, _c_void(cnt.data_ptr() + 8 * g0 * 2 * nb),
+        rc = lib.h2o_group_sketch(_ptr(p1), 1 if p1.dtype == torch.float64 else 0, _ptr(y), _ptr(g), n, nb, g0, gc,
+                                  float(thr), 1 if flip else 0, _c_void(cnt.data_ptr() + 8 * g0 * 2 * nb),
                                   _c_void(cm.data_ptr() + 8 * g0 * 4), _c_void(sums.data_ptr() + 8 * g0 * 2),
                                   int(max_blocks) if max_blocks else 0, stream)
-        if rc != 0:
-            raise RuntimeError(f"h2o_group_sketch failed: {rc}")
+        check(rc, "h2o_group_sketch")
         chunks += 1
     return SketchResult(cnt, cm, sums, True, None, chunks)

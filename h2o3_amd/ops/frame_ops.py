@@ -5,33 +5,19 @@ standardization).  Reference: water/fvec/RollupStats.java, hex/DataInfo.java.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _native
+from ._native import check as _check, ptr as _ptr, stream as _stream
 
 _FLOATS = (torch.float32, torch.float64)
 
 
 def _lib():
-    lib = _native.get_lib("frame", required=False)
-    if lib is not None and not getattr(lib, "_typed", False):
-        P, I, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-        lib.h2o_rollup_multi.argtypes = [P, I, LL, I, P, I, P, P]
-        lib.h2o_expand_numeric.argtypes = [P, I, LL, P, P, P, P, I, I, I, P]
-        lib._typed = True
-    return lib
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return _native.get_lib("frame", required=False)
 
 
 def _col_table(tensors, device):
@@ -100,8 +86,7 @@ def rollups_many(vecs) -> int:
                 if n > 0:
                     rc = lib.h2o_rollup_multi(_ptr(tab), nc, n, slices, None if mean_ is None else _ptr(mean_),
                                               pass_, _ptr(part), _stream())
-                    if rc != 0:
-                        raise RuntimeError(f"h2o_rollup_multi failed: {rc}")
+                    _check(rc, "h2o_rollup_multi")
                 else:
                     part.zero_()
                     part[..., 8] = float(np.finfo(np.float64).max)
@@ -154,8 +139,7 @@ def expand_numeric(tensors, plug, mean, sd, X, base) -> bool:
     pl, mu, s_ = f64(plug), f64(mean), f64(sd)
     rc = lib.h2o_expand_numeric(_ptr(tab), len(tensors), n, _ptr(pl), _ptr(mu), _ptr(s_), _ptr(X), X.shape[1],
                                 int(base), 0 if X.dtype == torch.float32 else 1, _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_expand_numeric failed: {rc}")
+    _check(rc, "h2o_expand_numeric")
     # (the tables are freed after the launch: the caching allocator only hands
     # their blocks to work queued after it on this stream)
     return True

@@ -11,28 +11,13 @@ import os
 import torch
 
 from . import _native
+from ._native import check as _check, ptr as _ptr, stream as _stream
 
 _pairs_cache = {}
 
 
 def _lib():
-    lib = _native.get_lib("gram")
-    if lib is not None and not getattr(lib, "_typed", False):
-        lib.h2o_gram.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p,
-                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        P, I, LL, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-        lib.h2o_glm_irls.argtypes = [P, LL, I, I, P, I, I, I, P, F, P, P, P, I, I, F, F, P, P, I, I, P, P, P, I, I, P]
-        lib.h2o_glm_irls_chunk.argtypes = [I]
-        lib.h2o_gram_split.argtypes = [P, I, I, I, P, P, LL, P, P]
-        lib.h2o_glm_wide_split.argtypes = [P, I, I, I, LL, P, F, P, P, P, I, I, F, F, P, P, I, P, P, P]
-        lib.h2o_glm_wide_gram.argtypes = [P, I, I, LL, P, I, I, P, I, P]
-        lib.h2o_glm_wide_split_grid.argtypes = [I]
-        lib.h2o_glm_wide_gram256.argtypes = [P, I, I, LL, P, I, I, P, I, I, P]
-        lib.h2o_gram_f64.argtypes = [P, I, I, LL, P, P, I, I, LL, P, P]
-        lib.h2o_xv_f64.argtypes = [P, I, I, LL, P, ctypes.c_double, P, P]
-        lib.h2o_xtr_f64.argtypes = [P, I, I, LL, P, I, LL, P, P]
-        lib._typed = True
-    return lib
+    return _native.get_lib("gram")
 
 
 def _pairs(T, device):
@@ -69,10 +54,6 @@ def glm_fused_codes(family, link, tlp=1.0):
 
 def _f32(t):
     return None if t is None else t.to(torch.float32).contiguous()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
 def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, codes=(0, 0), tvp=0.0, theta=1e-10,
@@ -122,9 +103,8 @@ def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, cod
                           float(theta), _ptr(keep[3]), _ptr(keep[4]), int(aug), int(bool(signed)), _ptr(out),
                           _ptr(dev), _ptr(gout), -1 if bf3 is None else (2 if bf3 == "bf16" else int(bool(bf3))),
                           int(bool(grad_f64)),
-                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"h2o_glm_irls failed: {rc}")
+                          _stream())
+    _check(rc, "h2o_glm_irls")
     G = _assemble(out.sum(0), pairs_t, T)
     if grad:
         return G, dev.sum(), gout.sum(0)
@@ -202,11 +182,7 @@ def weighted_gram(X: torch.Tensor, w: torch.Tensor | None = None, use_native=Non
     out = torch.empty((splits, npairs, 32, 32), dtype=torch.float64, device=X.device)
     X = X.contiguous()
     wt = None if w is None else w.to(torch.float32).contiguous()
-    rc = lib.h2o_gram(ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(wt.data_ptr() if wt is not None else 0), N, P,
-                      ctypes.c_void_p(pairs_t.data_ptr()), npairs, splits, rpb, ctypes.c_void_p(out.data_ptr()),
-                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"h2o_gram failed: {rc}")
+    _check(lib.h2o_gram(_ptr(X), _ptr(wt), N, P, _ptr(pairs_t), npairs, splits, rpb, _ptr(out), _stream()), "h2o_gram")
     return _assemble(out.sum(0), pairs_t, T)
 
 
@@ -256,11 +232,8 @@ def gram_f64_aug(X: torch.Tensor, P: int, W: torch.Tensor, part_budget: int = 1 
     Wd = W.to(torch.float64).contiguous()
     if Wd.numel() != N:
         raise ValueError("gram_f64_aug: W length differs from X rows")
-    rc = lib.h2o_gram_f64(ctypes.c_void_p(X.data_ptr()), X.stride(0), P, N, ctypes.c_void_p(Wd.data_ptr()),
-                          ctypes.c_void_p(pairs_t.data_ptr()), npairs, slabs, rps, ctypes.c_void_p(part.data_ptr()),
-                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"h2o_gram_f64 failed: {rc}")
+    _check(lib.h2o_gram_f64(_ptr(X), X.stride(0), P, N, _ptr(Wd), _ptr(pairs_t), npairs, slabs, rps, _ptr(part),
+                            _stream()), "h2o_gram_f64")
     return _assemble(part.sum(0), pairs_t, T)[:Pa, :Pa]
 
 
@@ -275,11 +248,7 @@ def xv_f64(X: torch.Tensor, P: int, beta: torch.Tensor, b0: float = 0.0) -> torc
     bt = beta.to(device=X.device, dtype=torch.float64).contiguous()
     if bt.numel() < P:
         raise ValueError("xv_f64: beta shorter than P")
-    rc = _lib().h2o_xv_f64(ctypes.c_void_p(X.data_ptr()), X.stride(0), P, N, ctypes.c_void_p(bt.data_ptr()),
-                           float(b0), ctypes.c_void_p(out.data_ptr()),
-                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"h2o_xv_f64 failed: {rc}")
+    _check(_lib().h2o_xv_f64(_ptr(X), X.stride(0), P, N, _ptr(bt), float(b0), _ptr(out), _stream()), "h2o_xv_f64")
     return out
 
 
@@ -299,11 +268,8 @@ def xtr_f64(X: torch.Tensor, P: int, r: torch.Tensor) -> torch.Tensor:
     rps = -(-N // slabs)
     slabs = -(-N // rps)
     part = torch.empty((slabs, P), dtype=torch.float64, device=X.device)
-    rc = _lib().h2o_xtr_f64(ctypes.c_void_p(X.data_ptr()), X.stride(0), P, N, ctypes.c_void_p(rv.data_ptr()), slabs,
-                            rps, ctypes.c_void_p(part.data_ptr()),
-                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"h2o_xtr_f64 failed: {rc}")
+    _check(_lib().h2o_xtr_f64(_ptr(X), X.stride(0), P, N, _ptr(rv), slabs, rps, _ptr(part), _stream()),
+           "h2o_xtr_f64")
     return part.sum(0)
 
 
@@ -399,14 +365,13 @@ def gram_aug_bf3(X, W, z, P, step=1 << 19):
     grp = min(nch, _WIDE_GROUP)
     HL = torch.empty((grp * st, 2 * Pa), dtype=torch.bfloat16, device=X.device)
     G = torch.zeros((Pa, Pa), dtype=torch.float64, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
     def split(i, a, r, buf, j, strm):
         rc = lib.h2o_gram_split(ctypes.c_void_p(X.data_ptr() + a * ldx * 4), ldx, P, Pa,
                                 ctypes.c_void_p(0 if W32 is None else W32.data_ptr() + a * 4),
                                 ctypes.c_void_p(0 if z32 is None else z32.data_ptr() + a * 4), r,
                                 ctypes.c_void_p(buf.data_ptr() + j * st * 2 * Pa * 2), strm)
-        if rc != 0:
-            raise RuntimeError(f"h2o_gram_split failed: {rc}")
+        _check(rc, "h2o_gram_split")
 
     if _overlap_ok(X, nch, grp):
         _pipelined_groups(split, HL, N, st, grp, Pa, G)
@@ -484,15 +449,14 @@ def wide_gram(X, P, wr, stream=None, bf3=True):
     fold = 1024 if bf3 or T != 256 else 1 << 30
     with phase("glm.wide_gram.zero"):
         part = torch.zeros((npairs * S, T, T), dtype=torch.float64, device=X.device)
-    stream = stream or ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = stream or _stream()
     with phase("glm.wide_gram.kernel"):
         if T == 256:
             rc = lib.h2o_glm_wide_gram256(_ptr(X), ldx, P, N, _ptr(wr), S, fold, _ptr(part), 0, int(bool(bf3)),
                                           stream)
         else:
             rc = lib.h2o_glm_wide_gram(_ptr(X), ldx, P, N, _ptr(wr), S, fold, _ptr(part), 0, stream)
-    if rc != 0:
-        raise RuntimeError(f"h2o_glm_wide_gram failed: {rc}")
+    _check(rc, "h2o_glm_wide_gram")
     with phase("glm.wide_gram.assemble"):
         return _wide_gram_assemble(part, S, NB, P, T)
 
@@ -552,7 +516,7 @@ def glm_wide_irls(X, P, beta, b0, y, wprior=None, offset=None, codes=(1, 1), tvp
         # reads each chunk's weights with scalar vector loads)
         wr = torch.empty(-(-N // 64) * 64, dtype=torch.float32, device=X.device)
         wr[N:].zero_()
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = _stream()
         offp = lambda t, a: ctypes.c_void_p(0 if t is None else t.data_ptr() + a * 4)
         with phase("glm.wide_eta"):
             for i, a in enumerate(range(0, N, st)):
@@ -561,8 +525,7 @@ def glm_wide_irls(X, P, beta, b0, y, wprior=None, offset=None, codes=(1, 1), tvp
                                             float(b0), offp(keep[0], a), offp(keep[1], a), offp(keep[2], a),
                                             int(codes[0]), int(codes[1]), float(tvp), float(theta), None,
                                             _ptr(dev[i]), blocks, _ptr(gbuf), offp(wr, a), stream)
-                if rc != 0:
-                    raise RuntimeError(f"h2o_glm_wide_split failed: {rc}")
+                _check(rc, "h2o_glm_wide_split")
         if eta_only:
             return None, dev.sum(), gbuf.sum(0)
         with phase("glm.wide_gram"):
@@ -574,7 +537,7 @@ def glm_wide_irls(X, P, beta, b0, y, wprior=None, offset=None, codes=(1, 1), tvp
     dev = torch.zeros((nch, blocks), dtype=torch.float64, device=X.device)
     gbuf = torch.zeros((blocks, Pa), dtype=torch.float64, device=X.device)
     G = torch.zeros((Pa, Pa), dtype=torch.float64, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
 
     def off(t, a):
         return ctypes.c_void_p(0 if t is None else t.data_ptr() + a * 4)
@@ -585,8 +548,7 @@ def glm_wide_irls(X, P, beta, b0, y, wprior=None, offset=None, codes=(1, 1), tvp
                                     int(codes[1]), float(tvp), float(theta),
                                     ctypes.c_void_p(buf.data_ptr() + j * st * 2 * Pa * 2), _ptr(dev[i]), blocks,
                                     _ptr(gbuf), None, strm)
-        if rc != 0:
-            raise RuntimeError(f"h2o_glm_wide_split failed: {rc}")
+        _check(rc, "h2o_glm_wide_split")
 
     if _overlap_ok(X, nch, grp):
         _pipelined_groups(split, HL, N, st, grp, Pa, G)

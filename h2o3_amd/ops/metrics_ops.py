@@ -4,21 +4,15 @@ grouped f64 sums, both with wave-aggregated atomics (hex/AUC2.java AUCBuilder, M
 MetricBuilderBinomial)."""
 from __future__ import annotations
 
-import ctypes
 
 import torch
 
 from . import _native
+from ._native import check as _check, ptr as _ptr, stream as _stream
 
 
 def _lib():
-    lib = _native.get_lib("metrics", required=False)
-    if lib is not None and not getattr(lib, "_typed", False):
-        P = ctypes.c_void_p
-        lib.h2o_logit_hist.argtypes = [P, P, P, ctypes.c_longlong, ctypes.c_int, P, P, P]
-        lib.h2o_group_reduce.argtypes = [P, P, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P]
-        lib._typed = True
-    return lib
+    return _native.get_lib("metrics", required=False)
 
 
 def available(t) -> bool:
@@ -39,13 +33,8 @@ def logit_hist(y, p1, w, nb):
         raise ValueError("logit_hist: y / p1 / w lengths differ")
     w = None if w is None else w.reshape(-1).to(device=p1.device, dtype=torch.float64).contiguous()
     buf = torch.zeros(2 * nb + 5, dtype=torch.float64, device=p1.device)
-    s = torch.cuda.current_stream().cuda_stream
-    rc = lib.h2o_logit_hist(ctypes.c_void_p(p1.data_ptr()), ctypes.c_void_p(y.data_ptr()),
-                            ctypes.c_void_p(w.data_ptr() if w is not None else 0), n, nb,
-                            ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(buf.data_ptr() + 16 * nb),
-                            ctypes.c_void_p(s))
-    if rc != 0:
-        raise RuntimeError(f"h2o_logit_hist failed ({rc})")
+    _check(lib.h2o_logit_hist(_ptr(p1), _ptr(y), _ptr(w), n, nb, _ptr(buf), _ptr(buf[2 * nb:]), _stream()),
+           "h2o_logit_hist")
     return buf
 
 
@@ -68,11 +57,7 @@ def group_reduce(idx, vals, nbins, op="sum"):
     out = torch.full((nbins, C), fill, dtype=torch.float64, device=v.device)
     if n == 0 or nbins == 0 or C == 0:
         return out
-    rc = lib.h2o_group_reduce(ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(v.data_ptr()), n, C, nbins, code,
-                              ctypes.c_void_p(out.data_ptr()),
-                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"h2o_group_reduce failed ({rc})")
+    _check(lib.h2o_group_reduce(_ptr(idx), _ptr(v), n, C, nbins, code, _ptr(out), _stream()), "h2o_group_reduce")
     return out
 
 

@@ -20,17 +20,11 @@ import numpy as np
 import torch
 
 from . import _native
+from ._native import check as _check, ptr as _ptr, stream as _stream
 
 MAX_COLS = 4                  # columns overridden together
 CHUNK = 64                    # grid points per launch: the bits of a uint64 mask
 MAX_DEPTH = 64                # deepest forest the kernel takes (splits on one path)
-_c_void = ctypes.c_void_p
-_c_int = ctypes.c_int
-_c_ll = ctypes.c_longlong
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 class GridResult:
@@ -79,22 +73,10 @@ def forest_grid_sums_torch(P, X, K, cols, grid):
     return out
 
 
-def _typed(lib):
-    if not getattr(lib, "_typed", False):
-        lib.h2o_forest_pd_chunk.argtypes = [_c_void, _c_ll, _c_int, _c_void, _c_int] + [_c_void] * 6 + \
-            [_c_int, _c_int, _c_void, _c_int, _c_void] + [_c_int] * 4 + [_c_void, _c_int, _c_void, _c_ll, _c_int,
-                                                                          _c_void]
-        lib.h2o_pd_block_threads.argtypes = [_c_int, _c_int]
-        lib.h2o_pd_lds_bytes.argtypes = [_c_int, _c_int, _c_int]
-        lib.h2o_pd_lds_bytes.restype = _c_ll
-        lib._typed = True
-    return lib
-
-
 def launch_shape(G, depth):
     """(threads per block, LDS bytes per block) of a kernel launch for a chunk
     of G <= 64 grid points on a forest of that depth."""
-    lib = _typed(_native.get_lib("tree_pd", required=True))
+    lib = _native.get_lib("tree_pd", required=True)
     sd = max(1, min(int(depth), int(G) - 1))
     th = lib.h2o_pd_block_threads(int(G), sd)
     return th, int(lib.h2o_pd_lds_bytes(th, int(G), sd))
@@ -145,9 +127,9 @@ def forest_grid_sums(P, X, K, cols, grid, row0=0, nrows=None) -> GridResult:
         return GridResult(out, True, None, 0)
     if int(P["feat"].max()) >= F:
         raise ValueError("forest_grid_sums: the forest splits on a feature the matrix does not have")
-    lib = _typed(_native.get_lib("tree_pd", required=True))
+    lib = _native.get_lib("tree_pd", required=True)
     X = X.contiguous().to(torch.float32)
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
     lmask = torch.empty(n_nodes, dtype=torch.int64, device=X.device)
     ccols = (ctypes.c_int * S)(*cols)
     base = ctypes.c_void_p(X.data_ptr() + 4 * row0)
@@ -164,6 +146,5 @@ def forest_grid_sums(P, X, K, cols, grid, row0=0, nrows=None) -> GridResult:
                                          _ptr(P["roots"]), _ptr(P["tclass"]), T, k, ccols, S, _ptr(grid), G, g0, gc,
                                          max_depth(P), _ptr(lmask), 1 if i == 0 else 0,
                                          ctypes.c_void_p(out.data_ptr() + 4 * g0 * n * K), n * K, K, stream)
-            if rc != 0:
-                raise RuntimeError(f"h2o_forest_pd_chunk failed: {rc}")
+            _check(rc, "h2o_forest_pd_chunk")
     return GridResult(out, True, None, chunks)

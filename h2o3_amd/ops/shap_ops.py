@@ -27,17 +27,10 @@ from fractions import Fraction
 import torch
 
 from . import _native
+from ._native import check as _check, ptr as _ptr, stream as _stream
 
 MAX_PATH = 32                 # path elements a uint32 mask holds
 _ROW_TILE_CAP = 32768         # test rows per tile (bounds the per-tile scratch)
-_c_void = ctypes.c_void_p
-_c_int = ctypes.c_int
-_c_ll = ctypes.c_longlong
-_c_dbl = ctypes.c_double
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
 class ShapResult:
@@ -161,16 +154,6 @@ def background_shap_torch(P, PT, X, Z, F, per_reference=False, vscale=1.0, tree_
 
 
 # ------------------------------------------------------------------ kernel
-def _typed(lib):
-    if not getattr(lib, "_typed", False):
-        lib.h2o_shap_masks.argtypes = [_c_void, _c_ll, _c_int] + [_c_void] * 11 + [_c_int] * 3 + \
-            [_c_void, _c_void, _c_dbl, _c_void]
-        lib.h2o_shap_pairs.argtypes = [_c_void, _c_int, _c_void, _c_int] + [_c_void] * 4 + [_c_int] * 3 + \
-            [_c_void, _c_void, _c_dbl, _c_void, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_void]
-        lib._typed = True
-    return lib
-
-
 def _plan(PT, N, B, max_scratch_bytes, with_scale):
     """Row tile, background tile and tree chunks whose scratch (uint32 masks
     [leaves, rows] for both frames, plus the f64 pair factors and the
@@ -235,11 +218,11 @@ def background_shap(P, PT, X, Z, F, per_reference=False, vscale=1.0, tree_class=
     if why is not None:
         phi, fz = background_shap_torch(P, PT, X, Z, F, per_reference, vscale, tree_class, pair_scale)
         return ShapResult(phi, fz, False, why)
-    lib = _typed(_native.get_lib("tree_shap", required=True))
+    lib = _native.get_lib("tree_shap", required=True)
     dev = X.device
     X = X.contiguous().to(torch.float32)
     Z = Z.contiguous().to(torch.float32)
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
     W = weight_table(MAX_PATH, dev)
     L = PT["L"]
     tree_args = (_ptr(P["node"]), _ptr(P["cat_off"]), _ptr(P["cat_len"]), _ptr(P["cat_bits"]),
@@ -251,8 +234,7 @@ def background_shap(P, PT, X, Z, F, per_reference=False, vscale=1.0, tree_class=
         base = ctypes.c_void_p(M.data_ptr() + 4 * c0)
         rc = lib.h2o_shap_masks(base, M.shape[1], n, *tree_args, l0, l1, _ptr(mask), _ptr(score),
                                 float(vscale), stream)
-        if rc != 0:
-            raise RuntimeError(f"h2o_shap_masks failed: {rc}")
+        _check(rc, "h2o_shap_masks")
 
     # link-space scores: the bias term, and the pair factors' inputs
     fz = torch.zeros(B, dtype=torch.float64, device=dev)
@@ -295,8 +277,7 @@ def background_shap(P, PT, X, Z, F, per_reference=False, vscale=1.0, tree_class=
                                         _ptr(PT["leaf_val"]), _ptr(PT["leaf_cls"]), int(tree_class), l0, l1,
                                         _ptr(W), _ptr(S), float(vscale), _ptr(phi), r0, b0, B, F,
                                         1 if per_reference else 0, stream)
-                if rc != 0:
-                    raise RuntimeError(f"h2o_shap_pairs failed: {rc}")
+                _check(rc, "h2o_shap_pairs")
                 events.append((e0, e1, mark()))
     if per_reference:
         phi.view(N, B, F + 1)[:, :, F] = fz.view(1, B)
@@ -375,15 +356,6 @@ def path_shap_torch(P, PT, X, F, vscale=1.0, tree_class=0):
     return phi
 
 
-def _typed_path(lib):
-    if not getattr(lib, "_typed_path", False):
-        lib.h2o_shap_path.argtypes = [_c_void, _c_int] + [_c_void] * 5 + [_c_int] * 3 + \
-            [_c_void, _c_dbl, _c_void, _c_ll, _c_int, _c_void]
-        lib.h2o_shap_path_lds_bytes.restype = _c_ll
-        lib._typed_path = True
-    return _typed(lib)
-
-
 def path_shap(P, PT, X, F, vscale=1.0, tree_class=0, max_scratch_bytes=1 << 30, timing=None) -> ShapResult:
     """Path-dependent TreeSHAP contributions of the F features for the rows X
     [F, N] (column-major float32): phi [N, F+1] f64 whose bias column is left
@@ -411,10 +383,10 @@ def path_shap(P, PT, X, F, vscale=1.0, tree_class=0, max_scratch_bytes=1 << 30, 
         why = f"a path has {PT['max_path']} distinct features, the kernel's masks hold {MAX_PATH}"
     if why is not None:
         return ShapResult(path_shap_torch(P, PT, X, F, vscale, tree_class), None, False, why)
-    lib = _typed_path(_native.get_lib("tree_shap", required=True))
+    lib = _native.get_lib("tree_shap", required=True)
     dev = X.device
     X = X.contiguous().to(torch.float32)
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
     C = path_coef_table(dev)
     rt, _, chunks = _plan(PT, N, 0, max_scratch_bytes, False)
     phi = torch.zeros((N, F + 1), dtype=torch.float64, device=dev)
@@ -440,14 +412,12 @@ def path_shap(P, PT, X, F, vscale=1.0, tree_class=0, max_scratch_bytes=1 << 30, 
                                     _ptr(PT["cond_off"]), _ptr(PT["cond_node"]), _ptr(PT["cond_left"]),
                                     _ptr(PT["leaf_val"]), _ptr(PT["leaf_cls"]), int(tree_class), l0, l1, _ptr(MX),
                                     _ptr(None), float(vscale), stream)
-            if rc != 0:
-                raise RuntimeError(f"h2o_shap_masks failed: {rc}")
+            _check(rc, "h2o_shap_masks")
             e1 = mark()
             rc = lib.h2o_shap_path(_ptr(MX), nr, _ptr(PT["el_off"]), _ptr(PT["el_feat"]), _ptr(PT["el_zero"]),
                                    _ptr(PT["leaf_val"]), _ptr(PT["leaf_cls"]), int(tree_class), l0, l1, _ptr(C),
                                    float(vscale), _ptr(phi), r0, F, stream)
-            if rc != 0:
-                raise RuntimeError(f"h2o_shap_path failed: {rc}")
+            _check(rc, "h2o_shap_path")
             events.append((e0, e1, mark()))
     if timing is not None:
         torch.cuda.synchronize()

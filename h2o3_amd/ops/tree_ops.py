@@ -6,20 +6,17 @@ on CPU and by the numerics tests.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _native
+from ._native import check as _check, ptr as _ptr, stream as _stream
 
 _LDS_BUDGET = 80 * 1024   # bytes of LDS histogram per workgroup (2+ WG / CU)
-_c_void = ctypes.c_void_p
-_c_int = ctypes.c_int
-_c_ll = ctypes.c_longlong
-
 
 
 # Upload sequence numbers: every staged upload gets the next number; the
@@ -108,10 +105,6 @@ def _h2d(a, dev):
     return _ring.upload(a, dev)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
 # Environment switches read on the per-level hot path: inside a tree build
 # (env_scope) each key is read once per tree, elsewhere every call reads
 # os.environ (tests flip switches between direct kernel calls).
@@ -144,47 +137,8 @@ class env_scope:
         return False
 
 
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_get_device = getattr(torch._C, "_cuda_getDevice", None)
-
-
-def _stream():
-    """Current HIP stream as a ctypes pointer (the raw C getters: ~10x cheaper
-    than torch.cuda.current_stream(), called for every kernel launch)."""
-    if _raw_stream is not None and _get_device is not None:
-        return ctypes.c_void_p(_raw_stream(_get_device()))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _lib():
-    lib = _native.get_lib("tree_hist")
-    if lib is not None and not getattr(lib, "_typed", False):
-        lib.h2o_hist_build.argtypes = [_c_void, _c_int, _c_int, _c_void, _c_void, _c_void, _c_void, _c_int,
-                                       _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, _c_void, _c_int, _c_int,
-                                       _c_int, _c_void, _c_int, _c_void, _c_void]
-        lib.h2o_hist_quad3.argtypes = [_c_void, _c_int, _c_void, _c_void, _c_void, _c_void, _c_int, _c_int, _c_int,
-                                       _c_int, ctypes.c_float, ctypes.c_float, _c_void, _c_int, _c_int, _c_int,
-                                       _c_void, _c_int, _c_ll, _c_int, _c_void, _c_void]
-        lib.h2o_hist_bm.argtypes = [_c_void, _c_int, _c_void, _c_void, _c_void, _c_void, _c_int, _c_int, _c_int,
-                                    _c_int, ctypes.c_float, ctypes.c_float, _c_void, _c_int, _c_int, _c_void, _c_int,
-                                    _c_ll, _c_int, _c_void, _c_void, _c_void, _c_void]
-        lib.h2o_hist_build_pk.argtypes = [_c_void, _c_int, _c_int, _c_void, _c_void, _c_void, _c_void, _c_int,
-                                          _c_int, _c_int, _c_int, ctypes.c_float, _c_ll, _c_void, _c_int, _c_int,
-                                          _c_void, _c_int, _c_void, _c_void]
-        lib.h2o_part_flags.argtypes = [_c_void, _c_int, _c_ll, _c_ll, _c_void, _c_void, _c_void, _c_int, _c_void,
-                                       _c_void, _c_int, _c_void, _c_void, _c_void]
-        lib.h2o_part_compact.argtypes = [_c_void, _c_void, _c_void, _c_int, _c_void, _c_void, _c_void, _c_void,
-                                         _c_void, _c_void, _c_void]
-        lib.h2o_part_count.argtypes = [_c_void, _c_int, _c_ll, _c_ll, _c_void, _c_void, _c_int, _c_void,
-                                       _c_void, _c_int, _c_void, _c_void]
-        lib.h2o_part_scatter.argtypes = [_c_void, _c_int, _c_ll, _c_ll, _c_void, _c_void, _c_int, _c_void,
-                                         _c_void, _c_int, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                         _c_void, _c_void]
-        lib.h2o_fill_nid.argtypes = [_c_void, _c_void, _c_int, _c_void, _c_void]
-        lib.h2o_hist_bm_set_ragged.argtypes = [_c_int]
-        lib.h2o_hist_bm_set_ragged.restype = None
-        lib._typed = True
-    return lib
+    return _native.get_lib("tree_hist")
 
 
 def bm_ragged() -> int:
@@ -197,8 +151,9 @@ def bm_ragged() -> int:
 
 
 def set_bm_ragged(lib, mode=None):
-    """Hand the switch to the library before a h2o_hist_bm launch (every
-    caller does, so the value of one caller never leaks into another's)."""
+    """Hand the switch to the library before a h2o_hist_bm launch
+    (launch_hist_bm, the one call site, does: the value of one caller never
+    leaks into another's)."""
     lib.h2o_hist_bm_set_ragged(bm_ragged() if mode is None else int(mode))
 
 
@@ -358,6 +313,80 @@ def hist_chunk(total, n_fg, target_blocks=None):
     return max(2048, -(-total // n_chunks))
 
 
+class HistPlan(NamedTuple):
+    """Launch plan of one histogram build (hist_plan)."""
+    kernel: str     # "bm" bin-major | "quad" grouped-lane | "pk" packed wide-code | "flat"
+    n_fg: int       # feature groups
+    width: int      # features per group (G / fgw / FG of the kernels)
+    pack: bool      # one packed (count, response) fixed-point word per LDS atomic
+    chunk: int      # rows per work item
+    threads: int    # workgroup size handed to the kernel (the bin-major kernel fixes its own)
+    mode: int
+    Bs: int
+
+    def scales(self, vmax):
+        """(s0, s1, pack_bq): fixed-point scales of the two channels for channel
+        maxima `vmax`, and the bound of the packed response field (-1: not packed)."""
+        s0, s1 = (fixed_point_scale(m, self.chunk) for m in vmax)
+        bq = -1
+        if self.pack:
+            s1, bq = _pack_scale(vmax[1], self.chunk)
+        return s0, s1, bq
+
+    def part(self, n_items, dev):
+        """Two-pass flush scratch of the bin-major kernel for n_items work items (bm_part)."""
+        return bm_part(n_items, self.n_fg, self.Bs, self.width, self.pack or self.mode == 2, dev)
+
+
+def hist_plan(bd, mode, unit_w, rows, target_blocks=None, quad_budget=_LDS_BUDGET, quad_threads=512,
+              grouped=None) -> HistPlan:
+    """Which histogram kernel runs over `rows` rows of `bd` and how: the one
+    place that combines bm_groups / quad_groups / feature_group, hist_chunk,
+    the fall-back of the packed paths (a chunk of 2^23 rows or more overflows
+    the packed count field: the unpacked layout runs, on the chunk already
+    chosen) and, through HistPlan.scales, the fixed-point scales.
+    grouped: the one-byte-code kernels (bin-major, else grouped-lane) apply;
+    None: decided from bd, mode and H2O3_HIST_KERNEL.  quad_budget /
+    quad_threads: LDS budget and workgroup size of the grouped-lane kernel."""
+    F, Fp, Bs = bd.F, bd.Fp, bd.Bs
+    if grouped is None:
+        grouped = bd.code_bytes == 1 and Fp % 4 == 0 and Bs <= 256 and mode in (0, 1, 2) and \
+            env("H2O3_HIST_KERNEL", "quad") == "quad"
+    # wide (2-byte) codes, 0/1 weights: one packed u64 LDS atomic per (row,
+    # feature) -- half the LDS per feature, so ~2x the features per workgroup
+    # and half the re-reads of the rows per level
+    pack = mode == 0 and unit_w and (grouped or bd.code_bytes == 2) and env("H2O3_HIST_PACK", "1") == "1"
+
+    def layout(pack):
+        if grouped:
+            bm = bm_groups(F, Fp, Bs, pack or mode == 2)
+            return ("bm",) + bm if bm is not None else ("quad",) + quad_groups(F, Fp, Bs, pack, quad_budget)
+        FG = feature_group(F, Bs, 2 if pack else mode, budget=_PK_BUDGET if pack else _LDS_BUDGET)
+        return "pk" if pack else "flat", (F + FG - 1) // FG, FG
+
+    kernel, n_fg, width = layout(pack)
+    chunk = hist_chunk(rows, n_fg, target_blocks)
+    if pack and chunk >= (1 << 23):
+        pack = False
+        kernel, n_fg, width = layout(False)
+    threads = 0 if kernel == "bm" else quad_threads if kernel == "quad" else 512 if chunk >= 8192 else 256
+    return HistPlan(kernel, n_fg, width, pack, chunk, threads, mode, Bs)
+
+
+def launch_hist_bm(lib, plan, bd, ridx, va, vb, work, n_work, scales, hist, n_slots, wyy, posv, part, need=None,
+                   cnts=None, ragged=None):
+    """h2o_hist_bm from a plan: n_work work items (cnts: their device-side
+    count, n_work then being the capacity) of `work` into hist [F, n_slots,
+    Bs, C]; the ragged-group switch is handed over first (`ragged`: a value
+    read earlier, e.g. before a graph capture)."""
+    set_bm_ragged(lib, ragged)
+    s0, s1, bq = scales
+    rc = lib.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), n_work, bd.F, 0, bd.Bs,
+                         s0, s1, _ptr(hist), n_slots, plan.mode, _ptr(wyy), 1 if posv else 0, bq, plan.width,
+                         _ptr(need), _ptr(cnts), _ptr(part), _stream())
+    _check(rc, f"h2o_hist_bm (F={bd.F}, Fp={bd.Fp}, G={plan.width})")
+
+
 def hist_build(bd, ridx, va, vb, mode, starts, counts, n_slots, use_native=None, target_blocks=None, vmax=None,
                want_wyy=False, posv=False, unit_w=False, need_mask=None):
     """Histograms of the row segments [starts[i], starts[i]+counts[i]) of
@@ -382,87 +411,45 @@ def hist_build(bd, ridx, va, vb, mode, starts, counts, n_slots, use_native=None,
     native = dev.type == "cuda" if use_native is None else use_native
     if native:
         lib = _lib()
-        kern = env("H2O3_HIST_KERNEL", "quad")
         total = int(sum(counts))
         if total == 0:
             return ret()
-        quad = bd.code_bytes == 1 and bd.Fp % 4 == 0 and bd.Bs <= 256 and kern == "quad" and mode in (0, 1, 2)
-        pack = quad and mode == 0 and unit_w and env("H2O3_HIST_PACK", "1") == "1"
         # H2O3_HIST_BIG=1 (A/B): one 1024-thread workgroup per CU with up to 160 KB of LDS histogram
         big = env("H2O3_HIST_BIG", "0") == "1"
-        qbudget = 156 * 1024 if big else _LDS_BUDGET
-        bm = None
-        if quad:
-            bm = bm_groups(bd.F, bd.Fp, bd.Bs, pack or mode == 2)
-            n_fg, fgw = bm if bm is not None else quad_groups(bd.F, bd.Fp, bd.Bs, pack, qbudget)
-        pkw = False
-        if not quad:
-            # wide (2-byte) codes, 0/1 weights: one packed u64 LDS atomic per
-            # (row, feature) -- half the LDS per feature, so ~2x the features
-            # per workgroup and half the re-reads of the rows per level
-            pkw = mode == 0 and unit_w and bd.code_bytes == 2 and env("H2O3_HIST_PACK", "1") == "1"
-            FG = feature_group(bd.F, bd.Bs, 2 if pkw else mode, budget=_PK_BUDGET if pkw else _LDS_BUDGET)
-            n_fg = (bd.F + FG - 1) // FG
-        chunk = hist_chunk(total, n_fg, target_blocks)
-        if pkw and chunk >= (1 << 23):
-            pkw = False
-            FG = feature_group(bd.F, bd.Bs, mode)
-            n_fg = (bd.F + FG - 1) // FG
-        if pack and chunk >= (1 << 23):
-            pack = False
-            bm = bm_groups(bd.F, bd.Fp, bd.Bs, mode == 2)
-            n_fg, fgw = bm if bm is not None else quad_groups(bd.F, bd.Fp, bd.Bs, False, qbudget)
-        items = make_work(starts, counts, range(n_slots), chunk)
+        plan = hist_plan(bd, mode, unit_w, total, target_blocks, quad_budget=156 * 1024 if big else _LDS_BUDGET,
+                         quad_threads=1024 if big else 512)
+        items = make_work(starts, counts, range(n_slots), plan.chunk)
         if len(items) == 0:
             return ret()
         work = _h2d(items, dev)
-
-        def _need(fg):
-            if need_mask is None:
-                return None
-            m = need_mask[:, :bd.F].to(device=dev, dtype=torch.bool)
+        need = None
+        if need_mask is not None:
+            fg = plan.width
+            need = need_mask[:, :bd.F].to(device=dev, dtype=torch.bool)
             ng = (bd.F + fg - 1) // fg
             if ng * fg > bd.F:
-                m = torch.cat([m, torch.zeros((m.shape[0], ng * fg - bd.F), dtype=torch.bool, device=dev)], 1)
-            return m.view(m.shape[0], ng, fg).any(2).to(torch.uint8).contiguous()
-        threads = 512 if chunk >= 8192 else 256
+                need = torch.cat([need, torch.zeros((need.shape[0], ng * fg - bd.F), dtype=torch.bool, device=dev)], 1)
+            need = need.view(need.shape[0], ng, fg).any(2).to(torch.uint8).contiguous()
         if vmax is None:
             vmax = channel_max(va, vb, mode)
-        s0, s1 = (fixed_point_scale(m, chunk) for m in vmax)
-        if quad:
-            bq = -1
-            if pack:
-                s1, bq = _pack_scale(vmax[1] if vb is None else max(vmax[1], 0.0), chunk)
-            need = _need(fgw)
-            if bm is not None:
-                part = bm_part(len(items), n_fg, bd.Bs, fgw, pack or mode == 2, dev)
-                set_bm_ragged(lib)
-                rc = lib.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), len(items),
-                                     bd.F, 0, bd.Bs, s0, s1, _ptr(hist), n_slots, mode, _ptr(wyy), 1 if posv else 0,
-                                     bq, fgw, _ptr(need), None, _ptr(part), _stream())
-                if rc != 0:
-                    raise RuntimeError(f"h2o_hist_bm failed: error {rc} (F={bd.F}, Fp={bd.Fp}, G={fgw})")
-                return ret()
+        s0, s1, bq = plan.scales(vmax)
+        posv = 1 if posv else 0
+        if plan.kernel == "bm":
+            launch_hist_bm(lib, plan, bd, ridx, va, vb, work, len(items), (s0, s1, bq), hist, n_slots, wyy, posv,
+                           plan.part(len(items), dev), need=need)
+        elif plan.kernel == "quad":
             rc = lib.h2o_hist_quad3(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), len(items),
-                                    bd.F, 0, bd.Bs, s0, s1, _ptr(hist), n_slots, mode, 1024 if big else 512, _ptr(wyy),
-                                    1 if posv else 0, bq, fgw, _ptr(need), _stream())
-            if rc != 0:
-                raise RuntimeError(f"h2o_hist_quad3 failed: error {rc} (F={bd.F}, Fp={bd.Fp}, fgw={fgw})")
-            return ret()
-        need = _need(FG)
-        if pkw:
-            s1p, bqp = _pack_scale(vmax[1] if vb is None else max(vmax[1], 0.0), chunk)
-            rc = lib.h2o_hist_build_pk(_ptr(bd.codes), bd.code_bytes, bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb),
-                                       _ptr(work), len(items), bd.F, FG, bd.Bs, s1p, bqp, _ptr(hist), n_slots,
-                                       threads, _ptr(wyy), 1 if posv else 0, _ptr(need), _stream())
-            if rc != 0:
-                raise RuntimeError(f"h2o_hist_build_pk failed: hip error {rc}")
-            return ret()
-        rc = lib.h2o_hist_build(_ptr(bd.codes), bd.code_bytes, bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work),
-                                len(items), bd.F, FG, bd.Bs, s0, s1, _ptr(hist), n_slots, mode, threads, _ptr(wyy),
-                                1 if posv else 0, _ptr(need), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_hist_build failed: hip error {rc}")
+                                    bd.F, 0, bd.Bs, s0, s1, _ptr(hist), n_slots, mode, plan.threads, _ptr(wyy), posv,
+                                    bq, plan.width, _ptr(need), _stream())
+            _check(rc, f"h2o_hist_quad3 (F={bd.F}, Fp={bd.Fp}, fgw={plan.width})")
+        elif plan.kernel == "pk":
+            _check(lib.h2o_hist_build_pk(_ptr(bd.codes), bd.code_bytes, bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb),
+                                         _ptr(work), len(items), bd.F, plan.width, bd.Bs, s1, bq, _ptr(hist), n_slots,
+                                         plan.threads, _ptr(wyy), posv, _ptr(need), _stream()), "h2o_hist_build_pk")
+        else:
+            _check(lib.h2o_hist_build(_ptr(bd.codes), bd.code_bytes, bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb),
+                                      _ptr(work), len(items), bd.F, plan.width, bd.Bs, s0, s1, _ptr(hist), n_slots,
+                                      mode, plan.threads, _ptr(wyy), posv, _ptr(need), _stream()), "h2o_hist_build")
         return ret()
     if posv:
         # expand position-ordered payloads to row order for the reference path
@@ -542,11 +529,6 @@ def pair_hist(bd, ridx, va, vb, mode, node_st, node_ct, pair_node, pair_feat, vm
         return torch.zeros((0, Bs, 2), dtype=torch.float64, device=dev), wyy_n
     if native:
         lib = _lib()
-        if not getattr(lib, "_typed_pair", False):
-            lib.h2o_pair_hist.argtypes = [_c_void, _c_int, _c_ll, _c_void, _c_void, _c_void, _c_void, _c_int,
-                                          _c_void, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, _c_void,
-                                          _c_void, _c_void]
-            lib._typed_pair = True
         pct = ct[pn]
         nch = np.maximum((pct + chunk - 1) // chunk, 0)
         live = pct > 0
@@ -567,11 +549,9 @@ def pair_hist(bd, ridx, va, vb, mode, node_st, node_ct, pair_node, pair_feat, vm
             if vmax is None:
                 vmax = channel_max(va, vb, mode)
             s0, s1 = (fixed_point_scale(m, min(chunk, int(pct.max()))) for m in vmax)
-            rc = lib.h2o_pair_hist(_ptr(bd.codes_col), bd.code_bytes, bd.codes_col.stride(0), _ptr(ridx), _ptr(va),
-                                   _ptr(vb), _ptr(work), len(items), _ptr(pfd), Bs, mode, 1 if posv else 0, s0, s1,
-                                   _ptr(Hp), _ptr(pwyy), _stream())
-            if rc != 0:
-                raise RuntimeError(f"h2o_pair_hist failed: {rc}")
+            _check(lib.h2o_pair_hist(_ptr(bd.codes_col), bd.code_bytes, bd.codes_col.stride(0), _ptr(ridx), _ptr(va),
+                                     _ptr(vb), _ptr(work), len(items), _ptr(pfd), Bs, mode, 1 if posv else 0, s0, s1,
+                                     _ptr(Hp), _ptr(pwyy), _stream()), "h2o_pair_hist")
         if wyy_n is not None:
             fi = np.nonzero(first)[0]
             wyy_n[_h2d(pn[fi], dev)] = pwyy[_h2d(fi.astype(np.int64), dev)]
@@ -621,11 +601,6 @@ def pair_hist_dev(bd, ridx, va, vb, mode, node_st, node_ct, sel, vmax, posv=Fals
     Returns (Hp [n*k, Bs, 2] f64, wyy [n] f64 or None, pfeat [n*k] int32)."""
     dev = ridx.device
     lib = _lib()
-    if not getattr(lib, "_typed_pair", False):
-        lib.h2o_pair_hist.argtypes = [_c_void, _c_int, _c_ll, _c_void, _c_void, _c_void, _c_void, _c_int,
-                                      _c_void, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, _c_void,
-                                      _c_void, _c_void]
-        lib._typed_pair = True
     st = np.asarray(node_st, dtype=np.int64)
     ct = np.asarray(node_ct, dtype=np.int64)
     n, k = sel.shape
@@ -662,10 +637,6 @@ def pair_hist_dev(bd, ridx, va, vb, mode, node_st, node_ct, sel, vmax, posv=Fals
     if m:
         s0, s1 = (fixed_point_scale(v, min(chunk, int(ct.max()))) for v in vmax)
         fn = lib.h2o_pair_hist4 if kp > 1 else lib.h2o_pair_hist
-        if kp > 1 and not getattr(lib, "_typed_pair4", False):
-            lib.h2o_pair_hist4.argtypes = lib.h2o_pair_hist.argtypes
-            lib.h2o_pair_hist4b.argtypes = lib.h2o_pair_hist.argtypes + [_c_void]
-            lib._typed_pair4 = True
         args = [_ptr(bd.codes_col), bd.code_bytes, bd.codes_col.stride(0), _ptr(ridx), _ptr(va), _ptr(vb),
                 _ptr(items), n_items, _ptr(pfeat), Bs, mode, 1 if posv else 0, s0, s1, _ptr(Hp), _ptr(pwyy),
                 _stream()]
@@ -674,8 +645,7 @@ def pair_hist_dev(bd, ridx, va, vb, mode, node_st, node_ct, sel, vmax, posv=Fals
             rc = lib.h2o_pair_hist4b(*args, _ptr(fbins))
         else:
             rc = fn(*args)
-        if rc != 0:
-            raise RuntimeError(f"h2o_pair_hist failed: {rc}")
+        _check(rc, "h2o_pair_hist")
     return Hp, (pwyy.view(n, k)[:, 0].contiguous() if want_wyy else None), pfeat
 
 
@@ -698,14 +668,9 @@ def gbm_grad(y, f, w, family, out=None, d=None):
         z.copy_(v)
         return z
     lib = _lib()
-    if not getattr(lib, "_typed_grad", False):
-        lib.h2o_gbm_grad.argtypes = [_c_void, _c_void, _c_void, _c_int, _c_ll, _c_void, _c_void, _c_void]
-        lib._typed_grad = True
     yc, fc = y.contiguous().to(torch.float32), f.contiguous().to(torch.float32)
     wc = w.contiguous().to(torch.float32) if w is not None else None
-    rc = lib.h2o_gbm_grad(_ptr(yc), _ptr(fc), _ptr(wc), mode, n, _ptr(z), _ptr(d), _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_gbm_grad failed: {rc}")
+    _check(lib.h2o_gbm_grad(_ptr(yc), _ptr(fc), _ptr(wc), mode, n, _ptr(z), _ptr(d), _stream()), "h2o_gbm_grad")
     return z
 
 
@@ -744,8 +709,7 @@ def partition(bd, ridx, ridx_out, feats, masks, starts, counts, use_native=None,
         else:
             rc = lib.h2o_part_count(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), nw, _ptr(feat_t),
                                     _ptr(masks), bd.Bs, _ptr(cnt), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_part_count failed: {rc}")
+        _check(rc, "h2o_part_count")
         # per-node exclusive scans of the chunk counts (chunks of a node are
         # consecutive in `items`), vectorized on the host
         cnt_h = cnt.cpu().numpy().astype(np.int64)
@@ -764,16 +728,13 @@ def partition(bd, ridx, ridx_out, feats, masks, starts, counts, use_native=None,
         roff_d = _h2d(roff, dev)
         pa, pb, pa_o, pb_o = payload if payload is not None else (None, None, None, None)
         if ballot:
-            rc = lib.h2o_part_compact(_ptr(ridx), _ptr(work), _ptr(fbase), nw, _ptr(flags), _ptr(loff_d),
-                                      _ptr(roff_d), _ptr(ridx_out), _ptr(pa), _ptr(pa_o), _stream())
-            if rc != 0:
-                raise RuntimeError(f"h2o_part_compact failed: {rc}")
+            _check(lib.h2o_part_compact(_ptr(ridx), _ptr(work), _ptr(fbase), nw, _ptr(flags), _ptr(loff_d),
+                                        _ptr(roff_d), _ptr(ridx_out), _ptr(pa), _ptr(pa_o), _stream()),
+                   "h2o_part_compact")
             return nleft.tolist()
-        rc = lib.h2o_part_scatter(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), nw, _ptr(feat_t),
-                                  _ptr(masks), bd.Bs, _ptr(loff_d), _ptr(roff_d), _ptr(ridx_out), _ptr(pa), _ptr(pb),
-                                  _ptr(pa_o), _ptr(pb_o), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_part_scatter failed: {rc}")
+        _check(lib.h2o_part_scatter(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), nw, _ptr(feat_t),
+                                    _ptr(masks), bd.Bs, _ptr(loff_d), _ptr(roff_d), _ptr(ridx_out), _ptr(pa), _ptr(pb),
+                                    _ptr(pa_o), _ptr(pb_o), _stream()), "h2o_part_scatter")
         return nleft.tolist()
     out = []
     for i, (st, ct) in enumerate(zip(starts, counts)):
@@ -813,9 +774,6 @@ def iota_i32(out) -> bool:
     lib = _lib()
     if lib is None or out.dtype != torch.int32 or not out.is_cuda or out.data_ptr() % 16:
         return False
-    if not getattr(lib, "_typed_iota", False):
-        lib.h2o_iota_i32.argtypes = [_c_void, ctypes.c_longlong, _c_void]
-        lib._typed_iota = True
     return lib.h2o_iota_i32(_ptr(out), out.numel(), _stream()) == 0
 
 
@@ -832,10 +790,6 @@ def partition_async(bd, ridx, ridx_out, feat_d, masks, starts, counts, chunk=Non
     dev = ridx.device
     n = len(starts)
     lib = _lib()
-    if not getattr(lib, "_typed_async", False):
-        lib.h2o_part_offsets.argtypes = [_c_void, _c_void, _c_int, _c_int, _c_void, _c_void, _c_void, _c_void,
-                                         _c_int, _c_int, _c_void]
-        lib._typed_async = True
     if chunk is None:
         chunk = _part_chunk(sum(counts))
     nleft = torch.empty(n, dtype=torch.int64, device=dev)   # zeroed by the offsets kernel
@@ -856,13 +810,9 @@ def partition_async(bd, ridx, ridx_out, feat_d, masks, starts, counts, chunk=Non
     fbase = buf[12 * nw:]
     if chunk % 64 == 0 and env("H2O3_PART_ITEMS", "dev") == "dev":
         # per-chunk records written on the device from the O(frontier) segment table
-        if not getattr(lib, "_typed_items", False):
-            lib.h2o_part_items.argtypes = [_c_void, _c_int, _c_int, _c_int, _c_void, _c_void, _c_void, _c_void]
-            lib._typed_items = True
         seg = _h2d(np.concatenate([st, ct, np.cumsum(nch) - nch, np.cumsum(wd) - wd]), dev)
-        rc = lib.h2o_part_items(_ptr(seg), n, chunk, nw, _ptr(work), _ptr(meta), _ptr(fbase), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_part_items failed: {rc}")
+        _check(lib.h2o_part_items(_ptr(seg), n, chunk, nw, _ptr(work), _ptr(meta), _ptr(fbase), _stream()),
+               "h2o_part_items")
     else:
         items = make_work(starts, counts, range(n), chunk)
         words = (items[:, 2].astype(np.int64) + 63) // 64
@@ -885,22 +835,16 @@ def partition_async(bd, ridx, ridx_out, feat_d, masks, starts, counts, chunk=Non
     else:
         codes, rs, fs = bd.codes, bd.Fp, 1
     flags = torch.empty(total_words + 1, dtype=torch.int64, device=dev)
-    rc = lib.h2o_part_flags(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), _ptr(fbase), nw,
-                            _ptr(feat_t), _ptr(masks), bd.Bs, _ptr(flags), _ptr(cnt), _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_part_flags failed: {rc}")
+    _check(lib.h2o_part_flags(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), _ptr(fbase), nw,
+                              _ptr(feat_t), _ptr(masks), bd.Bs, _ptr(flags), _ptr(cnt), _stream()), "h2o_part_flags")
     loff = torch.empty(nw, dtype=torch.int32, device=dev)
     roff = torch.empty(nw, dtype=torch.int32, device=dev)
     stride = pk.stride(0) if pk is not None else 0
-    rc = lib.h2o_part_offsets(_ptr(cnt), _ptr(meta), nw, n, _ptr(loff), _ptr(roff), _ptr(nleft), _ptr(pk),
-                              stride, pk_col, _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_part_offsets failed: {rc}")
+    _check(lib.h2o_part_offsets(_ptr(cnt), _ptr(meta), nw, n, _ptr(loff), _ptr(roff), _ptr(nleft), _ptr(pk),
+                                stride, pk_col, _stream()), "h2o_part_offsets")
     pa, _, pa_o, _ = payload if payload is not None else (None, None, None, None)
-    rc = lib.h2o_part_compact(_ptr(ridx), _ptr(work), _ptr(fbase), nw, _ptr(flags), _ptr(loff), _ptr(roff),
-                              _ptr(ridx_out), _ptr(pa), _ptr(pa_o), _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_part_compact failed: {rc}")
+    _check(lib.h2o_part_compact(_ptr(ridx), _ptr(work), _ptr(fbase), nw, _ptr(flags), _ptr(loff), _ptr(roff),
+                                _ptr(ridx_out), _ptr(pa), _ptr(pa_o), _stream()), "h2o_part_compact")
     return nleft
 
 
@@ -916,40 +860,24 @@ def hist_build_dev(bd, ridx, va, vb, mode, rec, rec_cols, starts, counts, vmax, 
     #items)) -- capacities n = len(starts) -- or None when the quad kernel does
     not apply (the caller then builds after the host sync as before)."""
     dev = ridx.device
-    if dev.type != "cuda" or bd.code_bytes != 1 or bd.Fp % 4 != 0 or bd.Bs > 256 or mode not in (0, 1, 2) or \
-            env("H2O3_HIST_KERNEL", "quad") != "quad":
+    if dev.type != "cuda":
+        return None
+    total = int(sum(counts))
+    plan = hist_plan(bd, mode, unit_w, (total + 1) // 2, target_blocks)   # the lighter children: <= half the rows
+    if plan.kernel not in ("bm", "quad"):
         return None
     lib = _lib()
-    if not getattr(lib, "_typed_dev", False):
-        lib.h2o_child_work.argtypes = [_c_void, _c_void, _c_void] + [_c_int] * 8 + [_c_void, _c_void, _c_void,
-                                                                                  _c_void]
-        lib.h2o_hist_quad4.argtypes = [_c_void, _c_int, _c_void, _c_void, _c_void, _c_void, _c_int, _c_int, _c_int,
-                                       _c_int, ctypes.c_float, ctypes.c_float, _c_void, _c_int, _c_int, _c_int,
-                                       _c_void, _c_int, _c_ll, _c_int, _c_void, _c_void, _c_void]
-        lib.h2o_hist_sibling_dev.argtypes = [_c_void, _c_void, _c_void, _c_int, _c_int, _c_int, _c_int, _c_int,
-                                             _c_int, _c_int, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void]
-        lib._typed_dev = True
     n = len(starts)
     C = channels(mode)
-    pack = mode == 0 and unit_w and env("H2O3_HIST_PACK", "1") == "1"
-    bm = bm_groups(bd.F, bd.Fp, bd.Bs, pack or mode == 2)
-    n_fg, fgw = bm if bm is not None else quad_groups(bd.F, bd.Fp, bd.Bs, pack)
-    total = int(sum(counts))
-    chunk = hist_chunk((total + 1) // 2, n_fg, target_blocks)   # the lighter children: <= half the rows
-    if pack and chunk >= (1 << 23):
-        pack = False
-        bm = bm_groups(bd.F, bd.Fp, bd.Bs, mode == 2)
-        n_fg, fgw = bm if bm is not None else quad_groups(bd.F, bd.Fp, bd.Bs, False)
+    chunk = plan.chunk
     cap = n + total // chunk + 1
     stc = np.concatenate([np.asarray(starts, dtype=np.int64), np.asarray(counts, dtype=np.int64)])
     stc_d = _h2d(stc, dev)
     ibuf = torch.empty(4 * cap + 3 * n + 2, dtype=torch.int32, device=dev)
     work, slots, cnts = ibuf[:4 * cap], ibuf[4 * cap:4 * cap + 3 * n], ibuf[4 * cap + 3 * n:]
     ok_c, nl_c, wl_c, wr_c = rec_cols
-    rc = lib.h2o_child_work(_ptr(stc_d), _ptr(stc_d[n:]), _ptr(rec), rec.stride(0), ok_c, nl_c, wl_c, wr_c, n, chunk,
-                            cap, _ptr(work), _ptr(slots), _ptr(cnts), _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_child_work failed: {rc}")
+    _check(lib.h2o_child_work(_ptr(stc_d), _ptr(stc_d[n:]), _ptr(rec), rec.stride(0), ok_c, nl_c, wl_c, wr_c, n, chunk,
+                              cap, _ptr(work), _ptr(slots), _ptr(cnts), _stream()), "h2o_child_work")
     nh = bd.F * n * bd.Bs * C
     want_wyy = mode == 0
     buf = torch.zeros(nh + (n if want_wyy else 0), dtype=torch.float64, device=dev)
@@ -957,24 +885,14 @@ def hist_build_dev(bd, ridx, va, vb, mode, rec, rec_cols, starts, counts, vmax, 
     wyy = buf[nh:] if want_wyy else None
     if vmax is None:
         vmax = channel_max(va, vb, mode)
-    s0, s1 = (fixed_point_scale(m, chunk) for m in vmax)
-    bq = -1
-    if pack:
-        s1, bq = _pack_scale(vmax[1] if vb is None else max(vmax[1], 0.0), chunk)
-    if bm is not None:
-        part = bm_part(cap, n_fg, bd.Bs, fgw, pack or mode == 2, dev)
-        set_bm_ragged(lib)
-        rc = lib.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), cap, bd.F, 0, bd.Bs,
-                             s0, s1, _ptr(Hb), n, mode, _ptr(wyy), 1 if posv else 0, bq, fgw, None, _ptr(cnts),
-                             _ptr(part), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_hist_bm failed: {rc}")
+    s0, s1, bq = plan.scales(vmax)
+    if plan.kernel == "bm":
+        launch_hist_bm(lib, plan, bd, ridx, va, vb, work, cap, (s0, s1, bq), Hb, n, wyy, posv, plan.part(cap, dev),
+                       cnts=cnts)
         return Hb, wyy, slots, cnts
-    rc = lib.h2o_hist_quad4(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), cap, bd.F, 0, bd.Bs,
-                            s0, s1, _ptr(Hb), n, mode, 512, _ptr(wyy), 1 if posv else 0, bq, fgw, None, _ptr(cnts),
-                            _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_hist_quad4 failed: {rc}")
+    _check(lib.h2o_hist_quad4(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), cap, bd.F, 0, bd.Bs,
+                              s0, s1, _ptr(Hb), n, mode, plan.threads, _ptr(wyy), 1 if posv else 0, bq, plan.width,
+                              None, _ptr(cnts), _stream()), "h2o_hist_quad4")
     return Hb, wyy, slots, cnts
 
 
@@ -987,10 +905,9 @@ def hist_sibling_dev(Hb, H_prev, slots, cnts, clamp_mask, wyy_b=None, wyy_prev=N
     H = torch.empty((F, 2 * nb, Bs, C), dtype=Hb.dtype, device=Hb.device)
     wyy = torch.empty(2 * nb, dtype=torch.float64, device=Hb.device) if wyy_b is not None else None
     Hp = H_prev.contiguous()
-    rc = lib.h2o_hist_sibling_dev(_ptr(Hb), _ptr(Hp), _ptr(slots), nb, Hp.shape[1], 2 * nb, F, Bs * C, C, clamp_mask,
-                                  _ptr(H), _ptr(wyy_b), _ptr(wyy_prev), _ptr(wyy), _ptr(cnts), _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_hist_sibling_dev failed: {rc}")
+    _check(lib.h2o_hist_sibling_dev(_ptr(Hb), _ptr(Hp), _ptr(slots), nb, Hp.shape[1], 2 * nb, F, Bs * C, C, clamp_mask,
+                                    _ptr(H), _ptr(wyy_b), _ptr(wyy_prev), _ptr(wyy), _ptr(cnts), _stream()),
+           "h2o_hist_sibling_dev")
     return H, wyy
 
 
@@ -999,20 +916,14 @@ def hist_sibling(Hb, H_prev, build_slots, der_slots, par_slots, n_front, clamp_m
     parent - built (clamped at 0 on the channels of clamp_mask).  Returns
     (H [F, n_front, Bs, C], wyy [n_front] or None)."""
     lib = _lib()
-    if not getattr(lib, "_typed_sib", False):
-        lib.h2o_hist_sibling.argtypes = [_c_void, _c_void, _c_void, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                                         _c_int, _c_void, _c_void, _c_void, _c_void, _c_void]
-        lib._typed_sib = True
     F, nb, Bs, C = Hb.shape
     H = torch.empty((F, n_front, Bs, C), dtype=Hb.dtype, device=Hb.device)
     slots = _h2d(np.asarray([build_slots, der_slots, par_slots], dtype=np.int32).reshape(-1), Hb.device)
     wyy = torch.empty(n_front, dtype=torch.float64, device=Hb.device) if wyy_b is not None else None
     Hb = Hb.contiguous()
     Hp = H_prev.contiguous()
-    rc = lib.h2o_hist_sibling(_ptr(Hb), _ptr(Hp), _ptr(slots), nb, Hp.shape[1], n_front, F, Bs * C, C, clamp_mask,
-                              _ptr(H), _ptr(wyy_b), _ptr(wyy_prev), _ptr(wyy), _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_hist_sibling failed: {rc}")
+    _check(lib.h2o_hist_sibling(_ptr(Hb), _ptr(Hp), _ptr(slots), nb, Hp.shape[1], n_front, F, Bs * C, C, clamp_mask,
+                                _ptr(H), _ptr(wyy_b), _ptr(wyy_prev), _ptr(wyy), _stream()), "h2o_hist_sibling")
     return H, wyy
 
 
@@ -1030,9 +941,7 @@ def fill_nid(ridx, leaf_ids, starts, counts, nrows, use_native=None):
         items = make_work(starts, counts, leaf_ids, 65536)
         if len(items):
             work = _h2d(items, dev)
-            rc = lib.h2o_fill_nid(_ptr(ridx), _ptr(work), len(items), _ptr(nid), _stream())
-            if rc != 0:
-                raise RuntimeError(f"h2o_fill_nid failed: {rc}")
+            _check(lib.h2o_fill_nid(_ptr(ridx), _ptr(work), len(items), _ptr(nid), _stream()), "h2o_fill_nid")
         return nid
     for lid, st, ct in zip(leaf_ids, starts, counts):
         nid[ridx[st: st + ct].long()] = lid
@@ -1072,9 +981,6 @@ def leaf_pass(ridx, z, w, leaf_ids, starts, counts, n_leaves, nrows, mode, chunk
     = unit weights), optionally fused with the nid fill.  Returns (nid, [L, 2] f64)."""
     dev = ridx.device
     lib = _lib()
-    if not getattr(lib, "_typed_leaf", False):
-        lib.h2o_leaf_pass.argtypes = [_c_void, _c_void, _c_void, _c_void, _c_int, _c_int, _c_void, _c_void, _c_void]
-        lib._typed_leaf = True
     out = torch.zeros((n_leaves, 2), dtype=torch.float64, device=dev)
     nid = torch.zeros(nrows, dtype=torch.int32, device=dev) if want_nid else None
     items = make_work(starts, counts, leaf_ids, chunk)
@@ -1083,10 +989,8 @@ def leaf_pass(ridx, z, w, leaf_ids, starts, counts, n_leaves, nrows, mode, chunk
     work = _h2d(items, dev)
     z = z.to(torch.float32).contiguous()
     w = None if w is None else w.to(torch.float32).contiguous()
-    rc = lib.h2o_leaf_pass(_ptr(ridx), _ptr(z), _ptr(w), _ptr(work), len(items), int(mode), _ptr(nid), _ptr(out),
-                           _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_leaf_pass failed: {rc}")
+    _check(lib.h2o_leaf_pass(_ptr(ridx), _ptr(z), _ptr(w), _ptr(work), len(items), int(mode), _ptr(nid), _ptr(out),
+                             _stream()), "h2o_leaf_pass")
     return nid, out
 
 
@@ -1094,17 +998,11 @@ def leaf_pos_sums(zpos, leaf_ids, starts, counts, n_leaves, mode, chunk=65536):
     """Per-leaf gamma sums from the position-ordered NaN-masked residual
     payload (contiguous reads).  Returns [L, 2] f64 on device."""
     lib = _lib()
-    if not getattr(lib, "_typed_lpos", False):
-        lib.h2o_leaf_pos.argtypes = [_c_void, _c_void, _c_int, _c_int, _c_void, _c_void]
-        lib.h2o_leaf_update.argtypes = [_c_void, _c_void, _c_int, _c_void, _c_void, _c_void]
-        lib._typed_lpos = True
     out = torch.zeros((n_leaves, 2), dtype=torch.float64, device=zpos.device)
     items = make_work(starts, counts, leaf_ids, chunk)
     if len(items):
         work = _h2d(items, zpos.device)
-        rc = lib.h2o_leaf_pos(_ptr(zpos), _ptr(work), len(items), int(mode), _ptr(out), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_leaf_pos failed: {rc}")
+        _check(lib.h2o_leaf_pos(_ptr(zpos), _ptr(work), len(items), int(mode), _ptr(out), _stream()), "h2o_leaf_pos")
     return out
 
 
@@ -1115,13 +1013,8 @@ def col_sample(n, elig_d, k, seed):
     dev = elig_d.device
     out = torch.empty((n, k), dtype=torch.int64, device=dev)
     lib = _lib()
-    if not getattr(lib, "_typed_csamp", False):
-        lib.h2o_col_sample.argtypes = [_c_int, _c_int, _c_void, _c_int, ctypes.c_ulonglong, _c_void, _c_void]
-        lib._typed_csamp = True
-    rc = lib.h2o_col_sample(int(n), int(elig_d.numel()), _ptr(elig_d), int(k), int(seed) & ((1 << 64) - 1),
-                            _ptr(out), _stream())
-    if rc != 0:
-        raise RuntimeError(f"h2o_col_sample failed: {rc}")
+    _check(lib.h2o_col_sample(int(n), int(elig_d.numel()), _ptr(elig_d), int(k), int(seed) & ((1 << 64) - 1),
+                              _ptr(out), _stream()), "h2o_col_sample")
     return out
 
 
@@ -1133,31 +1026,22 @@ def leaf_scatter(ridx, d, vals, leaf_ids, starts, counts, chunk=65536):
             d[ridx[st: st + ct].long()] = vals[lid]
         return d
     lib = _lib()
-    if not getattr(lib, "_typed_lscat", False):
-        lib.h2o_leaf_scatter.argtypes = [_c_void, _c_void, _c_int, _c_void, _c_void, _c_void]
-        lib._typed_lscat = True
     items = make_work(starts, counts, leaf_ids, chunk)
     if len(items):
         work = _h2d(items, d.device)
-        rc = lib.h2o_leaf_scatter(_ptr(ridx), _ptr(work), len(items), _ptr(vals), _ptr(d), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_leaf_scatter failed: {rc}")
+        _check(lib.h2o_leaf_scatter(_ptr(ridx), _ptr(work), len(items), _ptr(vals), _ptr(d), _stream()),
+               "h2o_leaf_scatter")
     return d
 
 
 def leaf_update(ridx, f, vals, leaf_ids, starts, counts, chunk=65536):
     """f[ridx[p]] += vals[leaf(p)] over the leaf segments (f: contiguous f32)."""
     lib = _lib()
-    if not getattr(lib, "_typed_lpos", False):
-        lib.h2o_leaf_pos.argtypes = [_c_void, _c_void, _c_int, _c_int, _c_void, _c_void]
-        lib.h2o_leaf_update.argtypes = [_c_void, _c_void, _c_int, _c_void, _c_void, _c_void]
-        lib._typed_lpos = True
     items = make_work(starts, counts, leaf_ids, chunk)
     if len(items):
         work = _h2d(items, f.device)
-        rc = lib.h2o_leaf_update(_ptr(ridx), _ptr(work), len(items), _ptr(vals), _ptr(f), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_leaf_update failed: {rc}")
+        _check(lib.h2o_leaf_update(_ptr(ridx), _ptr(work), len(items), _ptr(vals), _ptr(f), _stream()),
+               "h2o_leaf_update")
 
 
 def seg_sum2(ridx, a, b, leaf_ids, starts, counts, n_leaves, use_native=None, chunk=65536):
@@ -1167,18 +1051,14 @@ def seg_sum2(ridx, a, b, leaf_ids, starts, counts, n_leaves, use_native=None, ch
     native = dev.type == "cuda" if use_native is None else use_native
     if native:
         lib = _lib()
-        if not getattr(lib, "_typed_seg", False):
-            lib.h2o_seg_sum2.argtypes = [_c_void, _c_void, _c_void, _c_void, _c_int, _c_void, _c_void]
-            lib._typed_seg = True
         items = make_work(starts, counts, leaf_ids, chunk)
         if len(items) == 0:
             return out
         work = _h2d(items, dev)
         a = a.to(torch.float32).contiguous()
         b = None if b is None else b.to(torch.float32).contiguous()
-        rc = lib.h2o_seg_sum2(_ptr(ridx), _ptr(a), _ptr(b), _ptr(work), len(items), _ptr(out), _stream())
-        if rc != 0:
-            raise RuntimeError(f"h2o_seg_sum2 failed: {rc}")
+        _check(lib.h2o_seg_sum2(_ptr(ridx), _ptr(a), _ptr(b), _ptr(work), len(items), _ptr(out), _stream()),
+               "h2o_seg_sum2")
         return out
     for lid, st, ct in zip(leaf_ids, starts, counts):
         r = ridx[st: st + ct].long()

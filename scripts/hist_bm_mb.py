@@ -1,7 +1,6 @@
 """Micro-benchmark of the bin-major histogram kernel by level shape and phase
 (h2o_hist_bm_set_debug: 1 = no flush, 2 = no LDS atomics, 3 = loads only),
 for every lane mapping of the ragged last group (RAGGED=0,1,2,3: H2O3_HIST_BM_RAGGED)."""
-import ctypes
 import os
 import sys
 import time
@@ -13,7 +12,6 @@ from h2o3_amd.models.tree.binning import BinnedData  # noqa: E402
 from h2o3_amd.ops import tree_ops  # noqa: E402
 
 lib = tree_ops._lib()
-lib.h2o_hist_bm_set_debug.argtypes = [ctypes.c_int]
 for N in (12_500_000, 100_000_000):
     F, Fp, Bs = 100, 128, 256
     dev = "cuda"

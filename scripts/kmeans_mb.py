@@ -10,7 +10,6 @@ X = torch.randn((N, P), device="cuda")
 C = X[:k].double()
 a = torch.full((N,), -1, dtype=torch.int32, device="cuda")
 lib = cluster_ops._lib()
-lib.h2o_kmeans_set_debug.argtypes = [cluster_ops._ci]
 
 
 XA = cluster_ops.abs_bound(X) if os.environ.get("FX", "1") == "1" else None
@@ -27,7 +26,6 @@ def run(flags, G=None, reps=5):
     return (time.perf_counter() - t) / reps * 1e3
 
 
-lib.h2o_kmeans_resident_per_cu.argtypes = [cluster_ops._ci] * 3 + [cluster_ops._cf]
 print("resident/CU", lib.h2o_kmeans_resident_per_cu(k, P, 1, 1.0 if XA else 0.0), "fixed-point sums", XA is not None,
       flush=True)
 for f, name in [(0, "full"), (1, "no mfma"), (2, "no sums"), (4, "no rowstats"), (8, "no global loads"),

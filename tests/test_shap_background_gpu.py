@@ -134,10 +134,8 @@ def test_many_features(F):
     """Averaged mode's other two launch forms: per-row LDS sums above 64 KiB
     (F = 120) and, past the LDS of a CU (F = 320), global f64 atomics.  The
     forest splits on features spread over 0 .. F-1."""
-    import ctypes
     from h2o3_amd.ops import _native
     lib = _native.get_lib("tree_shap", required=True)
-    lib.h2o_shap_lds_bytes.restype = ctypes.c_longlong
     lds = lib.h2o_shap_lds_bytes(F)
     assert (64 << 10) < lds <= (160 << 10) if F == 120 else lds > (160 << 10)
     feats = [int(v) for v in np.linspace(0, F - 1, 20)]

@@ -3,7 +3,6 @@ the node recursion and the torch implementation of the leaf-path rule, both
 computed on CPU copies of the inputs, and against the scoring kernel's
 decisions (Forest.predict).  Model level: predict_contributions on the kernel
 against the same call under H2O3_TREE_SHAP=torch."""
-import ctypes
 
 import numpy as np
 import pandas as pd
@@ -185,7 +184,6 @@ def test_many_features(F):
     blocks, the last one ragged."""
     from h2o3_amd.ops import _native
     lib = _native.get_lib("tree_shap", required=True)
-    lib.h2o_shap_path_lds_bytes.restype = ctypes.c_longlong
     lds = lib.h2o_shap_path_lds_bytes(F)
     if F == 40:
         assert lds <= (64 << 10)

@@ -41,9 +41,6 @@ def _lib():
     from h2o3_amd.ops import _native
     lib = _native.get_lib("tree_split")
     assert lib is not None, "libtree_split.so not loaded"
-    cv, ci = ctypes.c_void_p, ctypes.c_int
-    lib.h2o_ua_range.argtypes = [cv, ci, ci, ci, cv, cv, cv]
-    lib.h2o_ua_fold.argtypes = [cv, ci, ci, ci, ci, cv, cv, ci, cv, cv, cv]
     return lib
 
 
