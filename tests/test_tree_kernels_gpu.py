@@ -149,6 +149,9 @@ def test_grow_async_matches_sync(monkeypatch):
 
 
 def test_forest_predict_matches_host():
+    """Scoring kernel against the torch walk on the same pack() of a trained
+    GBM.  Edge cases of the decision rule, and a reference that does not read
+    pack(), belong in test_forest_predict_gpu.py."""
     _need_gpu()
     import pandas as pd
     import h2o3_amd
@@ -178,7 +181,8 @@ def test_forest_predict_matches_host():
 
 def test_forest_predict_multiclass_and_leaf_ids_match_host():
     """Packed-node scoring kernel, K > 1 (per-class sums into out[r, k]) and
-    the leaf-id output, against the torch walk; categorical + NA splits."""
+    the leaf-id output, against the torch walk; categorical + NA splits.
+    Edge cases belong in test_forest_predict_gpu.py."""
     _need_gpu()
     import pandas as pd
     import h2o3_amd
