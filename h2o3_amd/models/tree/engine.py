@@ -1495,8 +1495,11 @@ class TreeGrower:
         na_left = opt == 1
         ar_n = torch.arange(n, device=h.device)
         # stats of the winning split
-        Lw = torch.where((opt == 2).view(n, 1), totnn[ar_n, fl],
-                         L[ar_n, fl, t.clamp(max=nt - 1)] + torch.where(na_left.view(n, 1), na[ar_n, fl], torch.zeros_like(na[ar_n, fl])))
+        if nt > 0:
+            Lw = torch.where((opt == 2).view(n, 1), totnn[ar_n, fl],
+                             L[ar_n, fl, t.clamp(max=nt - 1)] + torch.where(na_left.view(n, 1), na[ar_n, fl], torch.zeros_like(na[ar_n, fl])))
+        else:
+            Lw = totnn[ar_n, fl]                           # one non-NA bin: NA vs rest is the only candidate
         Tw = T[ar_n, fl]
         Rw = Tw - Lw
         # go-left masks over codes

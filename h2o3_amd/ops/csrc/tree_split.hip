@@ -16,6 +16,16 @@
 //
 // Criteria: CRIT 0 = H2O squared error on (w, wy) channels + node wYY total;
 //           CRIT 1 = second-order gain on (g, h) (XGBoost).
+//
+// Tie rule (the reference scan): among candidates of equal gain the lowest
+// index in [NA right | NA left | NA vs rest] wins, i.e. the lowest key
+// opt * 65536 + t.  Every arg-max step of split_kernel -- a lane walking its
+// 64-bin chunks, the wave reduction -- orders candidates by (gain, -key), as
+// cat_pair_kernel does with (gain, -k).  A threshold t >= 1 on an empty bin
+// (both channels zero) repeats the partition of t - 1, which has the lower
+// index, so the numeric searches skip it: the two gains are equal in exact
+// arithmetic only, and the parallel prefix sums would break that tie by their
+// rounding.
 #include "common.h"
 
 struct SplitRec {
@@ -28,6 +38,11 @@ struct SplitRec {
 
 __device__ __forceinline__ double shfl_up_d(double v, int d) {
   return __shfl_up(v, d, 64);
+}
+
+// candidate (g, key) against the best so far: larger gain, then lower key
+__device__ __forceinline__ bool beats(double g, int key, const SplitRec& best) {
+  return g > best.gain || (g == best.gain && key < best.opt * 65536 + best.t);
 }
 
 template <int CRIT>
@@ -104,6 +119,7 @@ __global__ __launch_bounds__(256) void split_kernel(const double* __restrict__ H
   for (int c0 = 0; c0 < B; c0 += 64) {
     const int b = c0 + lane;
     double vw = b < B ? h[2 * b] : 0.0, vy = b < B ? h[2 * b + 1] : 0.0;
+    const bool fresh = b == 0 || vw != 0.0 || vy != 0.0;   // not a repeat of threshold b - 1
     // inclusive wave scan
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -113,7 +129,7 @@ __global__ __launch_bounds__(256) void split_kernel(const double* __restrict__ H
     const double lw = carry_w + vw, ly = carry_y + vy;
     carry_w += __shfl(vw, 63, 64);
     carry_y += __shfl(vy, 63, 64);
-    if (b <= B - 2) {
+    if (b <= B - 2 && fresh) {
       const double rw = tw - lw, ry = ty - ly;
       // opt 0: NA right
       {
@@ -121,7 +137,7 @@ __global__ __launch_bounds__(256) void split_kernel(const double* __restrict__ H
         if (valid_split<CRIT>(lw, ly, RW, RY, min_rows, lam, mo)) {
           double g = score<CRIT>(lw, ly, lam, alpha) + score<CRIT>(RW, RY, lam, alpha) - sT;
           if (CRIT == 1) g = 0.5 * g - gamma;
-          if (g > best.gain) { best.gain = g; best.t = b; best.opt = 0; best.lw = lw; best.ly = ly; }
+          if (beats(g, b, best)) { best.gain = g; best.t = b; best.opt = 0; best.lw = lw; best.ly = ly; }
         }
       }
       if (has_na) {  // opt 1: NA left
@@ -129,12 +145,12 @@ __global__ __launch_bounds__(256) void split_kernel(const double* __restrict__ H
         if (valid_split<CRIT>(LW, LY, rw, ry, min_rows, lam, mo)) {
           double g = score<CRIT>(LW, LY, lam, alpha) + score<CRIT>(rw, ry, lam, alpha) - sT;
           if (CRIT == 1) g = 0.5 * g - gamma;
-          if (g > best.gain) { best.gain = g; best.t = b; best.opt = 1; best.lw = LW; best.ly = LY; }
+          if (beats(g, 65536 + b, best)) { best.gain = g; best.t = b; best.opt = 1; best.lw = LW; best.ly = LY; }
         }
       }
     }
   }
-  // opt 2: NA vs rest (lane 0 only; ties resolved in favour of lower bins)
+  // opt 2: NA vs rest (lane 0 only; the highest key, so strict >)
   if (lane == 0 && has_na && valid_split<CRIT>(tw, ty, nw, ny, min_rows, lam, mo)) {
     double g = score<CRIT>(tw, ty, lam, alpha) + score<CRIT>(nw, ny, lam, alpha) - sT;
     if (CRIT == 1) g = 0.5 * g - gamma;
@@ -146,7 +162,7 @@ __global__ __launch_bounds__(256) void split_kernel(const double* __restrict__ H
   } else {
     if (!(best.gain > 0)) best.gain = -INFINITY;
   }
-  // wave arg-max (prefer larger gain, then lower opt-major order like the reference scan)
+  // wave arg-max (the tie rule of the header)
   for (int o = 32; o > 0; o >>= 1) {
     const double og = __shfl_xor(best.gain, o, 64);
     const int ot = __shfl_xor(best.t, o, 64);
@@ -492,6 +508,8 @@ __global__ __launch_bounds__(256) void cat_pair_kernel(const double* __restrict_
   const int nts = min(nt, Bsc);
   if (!dead) {
     for (int i = tid; i < nts; i += 256) {
+      // numeric pair: a threshold on an empty bin repeats threshold i - 1 (see the tie rule above)
+      if (!cat && i > 0 && h[(size_t)i * C] == 0.0 && h[(size_t)i * C + 1] == 0.0) continue;
       const double lw = sk[i], ly = s1[i];
       const double rw = tw - lw, ry = ty - ly;
       {
