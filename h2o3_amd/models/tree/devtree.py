@@ -156,8 +156,6 @@ class DevTreeGBM:
         # histogram layout and fixed-point scales (static: the chunk sizes follow
         # from N exactly as the level loop's do for a full frontier)
         self.pack = tree_ops.env("H2O3_HIST_PACK", "1") == "1"
-        # lane mapping of a ragged last feature group: read here, before the graph is captured
-        self.ragged = tree_ops.bm_ragged()
         # a tree starts from ridx = iota: with max_depth >= 2 level 0 is always
         # compacted, so the root kernels take "row id = position" (a null
         # ridx) and nothing writes or reads the 4 N bytes of iota
@@ -165,15 +163,18 @@ class DevTreeGBM:
         # leaf values are read through ridx[0], which stays iota.  The
         # histogram kernel has id-free instances for the packed G = 64 layout
         # with 8 codes per lane (the default).
-        # one plan for the root at N rows, one for the lighter children at half
+        # one plan for the root at N rows, one for the lighter children at half;
+        # they read the launch switches (codes per lane, lane mapping of a ragged
+        # last feature group) here, before the graph is captured
         self.plan_r = tree_ops.hist_plan(bd, 0, True, N, grouped=True)
         self.plan_c = tree_ops.hist_plan(bd, 0, True, (N + 1) // 2, grouped=True)
+        self.ragged = self.plan_r.ragged
         if self.pack and not (self.plan_r.pack and self.plan_c.pack):
             raise RuntimeError("devtree: histogram chunk too large for the packed path")
         n_fg, G = self.plan_r.n_fg, self.plan_r.width
         self.n_fg, self.G = n_fg, G
         self.root_ident = D >= 2 and tree_ops.env("H2O3_DEV_ROOT_IDENT", "1") != "0" and self.pack and G == 64 \
-            and tree_ops.env("H2O3_HIST_BM_LW", "2") != "1"
+            and self.plan_r.lw == 2
         self.chunk_r, self.chunk_c = self.plan_r.chunk, self.plan_c.chunk
         self.chunk_p = tree_ops._part_chunk(N)
         self.chunk_l = 65536
@@ -328,8 +329,7 @@ class DevTreeGBM:
             buf = self.Hroot
             buf.zero_()
             tree_ops.launch_hist_bm(lh, self.plan_r, bd, self._ridx(0, cur), self.pos[cur], None, self.hwork,
-                                    self.cap_r, self.sc_r, buf, 1, buf[nh:], True, self.part, cnts=self.counts,
-                                    ragged=self.ragged)
+                                    self.cap_r, self.sc_r, buf, 1, buf[nh:], True, self.part, cnts=self.counts)
             Hl, wl = buf[:nh].view(bd.F, 1, Bs, C), buf[nh:]
             if self.W > 1:
                 Hl, wl = self.drv.grower._rs_hist_wyy(Hl, wl)
@@ -344,8 +344,7 @@ class DevTreeGBM:
         buf = self.Hb[:nhb + npar]
         buf.zero_()
         tree_ops.launch_hist_bm(lh, self.plan_c, bd, self.ridx[cur], self.pos[cur], None, self.hwork, self.cap_c,
-                                self.sc_c, buf, npar, buf[nhb:], True, self.part, cnts=self.counts,
-                                ragged=self.ragged)
+                                self.sc_c, buf, npar, buf[nhb:], True, self.part, cnts=self.counts)
         Hb, wb = buf[:nhb].view(bd.F, npar, Bs, C), buf[nhb:]
         if self.W > 1:
             Hb, wb = self.drv.grower._rs_hist_wyy(Hb, wb)
@@ -399,9 +398,9 @@ class DevTreeGBM:
         _ck(lh.h2o_dt_items2(0, _ptr(recl), n, self.D, 0, self.chunk_p, self.cap_p, _ptr(self.pwork),
                              _ptr(self.fbase), _ptr(self.slot_wb) if skip else None, _ptr(self.counts), s),
             "dt_items(part)")
-        _ck(lh.h2o_part_flags_dev(_ptr(self.pcodes), 1, self.prs, self.pfs, _ptr(self._ridx(d, cur)),
-                                  _ptr(self.pwork), _ptr(self.fbase), self.cap_p, _ptr(self.feat_i), _ptr(self.mask),
-                                  Bs, _ptr(self.flags), _ptr(self.cnt), _ptr(self.counts), s), "part_flags_dev")
+        _ck(lh.h2o_part_flags(_ptr(self.pcodes), 1, self.prs, self.pfs, _ptr(self._ridx(d, cur)),
+                              _ptr(self.pwork), _ptr(self.fbase), self.cap_p, _ptr(self.feat_i), _ptr(self.mask),
+                              Bs, _ptr(self.flags), _ptr(self.cnt), _ptr(self.counts), s), "part_flags")
         _ck(lh.h2o_dt_offsets(_ptr(self.cnt), _ptr(self.pwork), _ptr(self.counts), _ptr(recl), n,
                               _ptr(self._rec_lvl(d + 1)), _ptr(self.loff), _ptr(self.roff), s), "dt_offsets")
         if skip:
@@ -416,10 +415,10 @@ class DevTreeGBM:
         if d == 0 and self.root_ident:
             # a root that stays a leaf is read back through ridx[0] when the depth is odd
             _ck(lh.h2o_dt_root_leaf_iota(_ptr(recl), _ptr(self.ridx[0]), self.N, s), "dt_root_leaf_iota")
-        _ck(lh.h2o_part_compact_dev(_ptr(self._ridx(d, cur)), _ptr(self.pwork), _ptr(self.fbase), self.cap_p,
-                                    _ptr(self.flags), _ptr(self.loff), _ptr(self.roff), _ptr(self.ridx[nxt]),
-                                    _ptr(self.pos[cur]), _ptr(self.pos[nxt]), _ptr(self.counts), s),
-            "part_compact_dev")
+        _ck(lh.h2o_part_compact(_ptr(self._ridx(d, cur)), _ptr(self.pwork), _ptr(self.fbase), self.cap_p,
+                                _ptr(self.flags), _ptr(self.loff), _ptr(self.roff), _ptr(self.ridx[nxt]),
+                                _ptr(self.pos[cur]), _ptr(self.pos[nxt]), _ptr(self.counts), s),
+            "part_compact")
         return nxt
 
     def _sequence(self):
@@ -443,8 +442,8 @@ class DevTreeGBM:
         s = _stream()
         _ck(lh.h2o_dt_items(3 if self.last_level else 2, _ptr(self.rec), self.nh, self.D, 0, self.chunk_l, self.cap_l,
                             _ptr(self.lwork), None, _ptr(self.counts), s), "dt_items(leaf)")
-        _ck(lh.h2o_leaf_pos_dev(_ptr(self.pos[cur]), _ptr(self.lwork), self.cap_l, 1 if self.bern else 0,
-                                _ptr(self.sums), _ptr(self.counts), s), "leaf_pos_dev")
+        _ck(lh.h2o_leaf_pos(_ptr(self.pos[cur]), _ptr(self.lwork), self.cap_l, 1 if self.bern else 0,
+                            _ptr(self.sums), _ptr(self.counts), s), "leaf_pos")
         if self.W > 1:
             coll.allreduce_(self.sums)
         s = _stream()

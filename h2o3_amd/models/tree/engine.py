@@ -1122,13 +1122,9 @@ class TreeGrower:
                                     wyy_n.repeat_interleave(k) if wyy_n is not None else None, raw=True,
                                     pbins=nb_t[fl] if nb_t is not None else None)
         xgb = 1 if p.criterion == "xgb" else 0
-        if nb_t is not None:
-            rc = lib.h2o_pair_select2(ptr(Hp), n, Bs, k, ptr(best_k), ptr(pfeat), ptr(self._fcat_u8), xgb, min_w2,
-                                      pk.stride(0), ptr(pk), ptr(mask), ptr(feat_i), ptr(nb_t), stream())
-        else:
-            rc = lib.h2o_pair_select(ptr(Hp), n, Bs, k, ptr(best_k), ptr(pfeat), ptr(self._fcat_u8), xgb, min_w2,
-                                     pk.stride(0), ptr(pk), ptr(mask), ptr(feat_i), stream())
-        check(rc, "h2o_pair_select")
+        check(lib.h2o_pair_select(ptr(Hp), n, Bs, k, ptr(best_k), ptr(pfeat), ptr(self._fcat_u8), xgb, min_w2,
+                                  pk.stride(0), ptr(pk), ptr(mask), ptr(feat_i), ptr(nb_t), stream()),
+              "h2o_pair_select")
 
     def _pair_direct_part(self, ridx, va, vb, mode, posv, st, ct, pn, pf):
         p = self.p

@@ -71,31 +71,27 @@ _TABLE = {
         h2o_group_reduce  i  PPqiiiPP
     """,
     "tree_hist": """
-        h2o_hist_quad4          i  PiPPPPiiiiffPiiiPiqiPPP
-        h2o_hist_quad3          i  PiPPPPiiiiffPiiiPiqiPP
+        h2o_hist_quad           i  PiPPPPiiiiffPiiiPiqiiPPP
         h2o_hist_bm_set_debug   v  i
-        h2o_hist_bm_set_ragged  v  i
-        h2o_hist_bm             i  PiPPPPiiiiffPiiPiqiPPPP
+        h2o_hist_bm             i  PiPPPPiiiiffPiiPiqiiiPPPP
         h2o_iota_i32            i  PqP
         h2o_hist_build          i  PiiPPPPiiiiffPiiiPiPP
         h2o_hist_build_pk       i  PiiPPPPiiiifqPiiPiPP
-        h2o_part_flags          i  PiqqPPPiPPiPPP
-        h2o_hist_sibling        i  PPPiiiiiiiPPPPP
-        h2o_hist_sibling_dev    i  PPPiiiiiiiPPPPPP
+        h2o_part_flags          i  PiqqPPPiPPiPPPP
+        h2o_hist_sibling        i  PPPiiiiiiiPPPPPP
         h2o_child_work          i  PPPiiiiiiiiPPPP
         h2o_part_offsets        i  PPiiPPPPiiP
-        h2o_part_compact        i  PPPiPPPPPPP
+        h2o_part_compact        i  PPPiPPPPPPPP
         h2o_part_count          i  PiqqPPiPPiPP
         h2o_part_scatter        i  PiqqPPiPPiPPPPPPPP
         h2o_fill_nid            i  PPiPP
         h2o_leaf_pass           i  PPPPiiPPP
         h2o_seg_sum2            i  PPPPiPP
-        h2o_leaf_pos            i  PPiiPP
+        h2o_leaf_pos            i  PPiiPPP
         h2o_col_sample          i  iiPiQPP
         h2o_leaf_scatter        i  PPiPPP
         h2o_leaf_update         i  PPiPPP
-        h2o_pair_hist4          i  PiqPPPPiPiiiffPPP
-        h2o_pair_hist4b         i  PiqPPPPiPiiiffPPPP
+        h2o_pair_hist4          i  PiqPPPPiPiiiffPPPP
         h2o_pair_hist           i  PiqPPPPiPiiiffPPP
         h2o_gbm_grad            i  PPPiqPPP
         h2o_part_items          i  PiiiPPPP
@@ -106,9 +102,6 @@ _TABLE = {
         h2o_dt_leaf_vals        i  PPiiPdPP
         h2o_dt_root             i  PqP
         h2o_dt_root_leaf_iota   i  PPqP
-        h2o_part_flags_dev      i  PiqqPPPiPPiPPPP
-        h2o_part_compact_dev    i  PPPiPPPPPPPP
-        h2o_leaf_pos_dev        i  PPiiPPP
         h2o_leaf_scatter_dev    i  PPiPPPP
         h2o_leaf_flag_sums_dev  i  PPPiPPiiPPP
         h2o_leaf_gather_lds     i  ii
@@ -138,8 +131,7 @@ _TABLE = {
         h2o_split_select2  i  PPiiiidiPPPP
         h2o_cat_pairs      i  PiiiiPPPPPdddddiPP
         h2o_cat_pairs2     i  PiiiiPPPPPdddddiPPiPP
-        h2o_pair_select    i  PiiiPPPidiPPPP
-        h2o_pair_select2   i  PiiiPPPidiPPPPP
+        h2o_pair_select    i  PiiiPPPidiPPPPP
         h2o_ua_range       i  PiiiPPP
         h2o_ua_fold        i  PiiiiPPiPPP
     """,

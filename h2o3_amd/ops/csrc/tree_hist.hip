@@ -196,7 +196,7 @@ __global__ __launch_bounds__(512) void hist_build_kernel(
 // unpipelined loop: SQ_WAIT_ANY = 69% of wave cycles, waves parked on the
 // dependent ridx -> codes gathers; pipelined: root 6.8 -> 5.5 ms, depth-3
 // level 4.2 -> 2.9 ms at 100M x 100).  Loads use clamped indices, so no
-// branch guards them.
+// branch guards them.  The host launches PIPE = true only.
 // ---------------------------------------------------------------------------
 template <int LW> struct CodeW { using T = unsigned int; };
 template <> struct CodeW<2> { using T = uint2; };
@@ -367,69 +367,49 @@ struct QuadArgs {
   const uint8_t* cc; int Fp; const int* ridx; const float* va; const float* vb; const int4* wk;
   int n_work, n_fg, fgw, F, foff, Bs; float s0, s1; double* hist; int n_slots; double* wyy; long long bq;
   const uint8_t* need; const int* n_work_dev; unsigned long long* part = nullptr;
+  int lw = 1;                          // code dwords per lane (1 -> 4 codes, 2 -> 8)
   int t_lw = 0, t_lpr = 0, t_ss = 0;   // hist_bm_kernel: ragged mapping of the last group (t_lw = 0: none)
 };
 
-template <int M, bool V, bool PV, bool PK, bool PIPE = true, int LW = 1>
+template <int M, bool V, bool PV, bool PK, int LW>
 static void lq(const QuadArgs& a) {
-  hipLaunchKernelGGL((hist_quad_kernel<M, V, PV, PK, PIPE, LW>), a.grid, dim3(a.threads), a.lds, a.s, a.cc, a.Fp,
+  hipLaunchKernelGGL((hist_quad_kernel<M, V, PV, PK, true, LW>), a.grid, dim3(a.threads), a.lds, a.s, a.cc, a.Fp,
                      a.ridx, a.va, a.vb, a.wk, a.n_work, a.n_fg, a.fgw, a.F, a.foff, a.Bs, a.s0, a.s1, a.hist,
                      a.n_slots, a.wyy, a.bq, a.need, a.n_work_dev);
 }
 
-static int env_int(const char* k, int d) {
-  const char* v = getenv(k);
-  return v ? atoi(v) : d;
-}
-
-// A/B switches: H2O3_HIST_PIPE=0 (unpipelined loop), H2O3_HIST_LW=2 (8 codes
-// per lane: one dwordx2 gather; measured 0-6% faster on scattered deep levels,
-// 5-10% slower at the contiguous root, off by default)
+// a.lw = 2: 8 codes per lane, one dwordx2 gather (measured 0-6% faster on
+// scattered deep levels, 5-10% slower at the contiguous root, so not the default)
 template <int M, bool V, bool PV, bool PK>
-static void lq_var(int lw, const QuadArgs& a) {
-  static const int pipe = env_int("H2O3_HIST_PIPE", 1);
-  if (!pipe) lq<M, V, PV, PK, false>(a);
-  else if (lw == 2) lq<M, V, PV, PK, true, 2>(a);
-  else lq<M, V, PV, PK>(a);
+static void lq_var(const QuadArgs& a) {
+  if (a.lw == 2) lq<M, V, PV, PK, 2>(a);
+  else lq<M, V, PV, PK, 1>(a);
 }
 
 template <int M, bool V>
-static void lq_pv(int posv, int pack, int lw, const QuadArgs& a) {
-  if (pack) { if (posv) lq_var<M, V, true, true>(lw, a); else lq_var<M, V, false, true>(lw, a); }
-  else { if (posv) lq_var<M, V, true, false>(lw, a); else lq_var<M, V, false, false>(lw, a); }
+static void lq_pv(int posv, int pack, const QuadArgs& a) {
+  if (pack) { if (posv) lq_var<M, V, true, true>(a); else lq_var<M, V, false, true>(a); }
+  else { if (posv) lq_var<M, V, true, false>(a); else lq_var<M, V, false, false>(a); }
 }
 
 // Histograms of features [foff, F) in n_fg = ceil((F - foff) / fgw) groups of
 // fgw features (a multiple of 4, at most 64; tree_ops.quad_groups picks it).
 // pack_bq >= 0 selects the packed single-atomic path (MODE 0, 0/1 weights).
-extern "C" int h2o_hist_quad4(const void* codes, int Fp, const int* ridx, const float* va, const float* vb,
-                              const int* work, int n_work, int F, int foff, int Bs, float s0, float s1,
-                              double* hist, int n_slots, int mode, int threads, double* wyy, int posv,
-                              long long pack_bq, int fgw, const uint8_t* need, const int* n_work_dev,
-                              hipStream_t s);
-extern "C" int h2o_hist_quad3(const void* codes, int Fp, const int* ridx, const float* va, const float* vb,
-                              const int* work, int n_work, int F, int foff, int Bs, float s0, float s1,
-                              double* hist, int n_slots, int mode, int threads, double* wyy, int posv,
-                              long long pack_bq, int fgw, const uint8_t* need, hipStream_t s) {
-  return h2o_hist_quad4(codes, Fp, ridx, va, vb, work, n_work, F, foff, Bs, s0, s1, hist, n_slots, mode, threads,
-                        wyy, posv, pack_bq, fgw, need, nullptr, s);
-}
-
+// lw = 2 asks for 8 codes per lane (honoured when fgw, foff and Fp are
+// multiples of 8, so that every dwordx2 read lies inside the row).
 // n_work_dev != nullptr: n_work is the CAPACITY of the device-built work list
 // (grid upper bound); the real count is n_work_dev[1].
-extern "C" int h2o_hist_quad4(const void* codes, int Fp, const int* ridx, const float* va, const float* vb,
-                              const int* work, int n_work, int F, int foff, int Bs, float s0, float s1,
-                              double* hist, int n_slots, int mode, int threads, double* wyy, int posv,
-                              long long pack_bq, int fgw, const uint8_t* need, const int* n_work_dev,
-                              hipStream_t s) {
+extern "C" int h2o_hist_quad(const void* codes, int Fp, const int* ridx, const float* va, const float* vb,
+                             const int* work, int n_work, int F, int foff, int Bs, float s0, float s1,
+                             double* hist, int n_slots, int mode, int threads, double* wyy, int posv,
+                             long long pack_bq, int fgw, int lw, const uint8_t* need, const int* n_work_dev,
+                             hipStream_t s) {
   if (n_work <= 0 || foff >= F) return 0;
   if (Fp % 4 != 0 || foff % 4 != 0 || Bs > 256 || mode < 0 || mode > 2) return -1;
   if (fgw < 4 || fgw > 64 || fgw % 4 != 0) return -2;
   const bool pack = pack_bq >= 0 && mode == 0;
   const int n_fg = (F - foff + fgw - 1) / fgw;
   if (foff + n_fg * fgw > Fp) return -3;       // every code dword read lies inside the row
-  static const int lw_env = env_int("H2O3_HIST_LW", 1);
-  const int lw = (lw_env == 2 && fgw % 8 == 0 && foff % 8 == 0 && Fp % 8 == 0) ? 2 : 1;
   const int C = mode == 2 ? 1 : 2;
   const int CL = pack ? 1 : C;
   QuadArgs a;
@@ -439,10 +419,11 @@ extern "C" int h2o_hist_quad4(const void* codes, int Fp, const int* ridx, const 
   a.cc = (const uint8_t*)codes; a.Fp = Fp; a.ridx = ridx; a.va = va; a.vb = vb; a.wk = (const int4*)work;
   a.n_work = n_work; a.n_fg = n_fg; a.fgw = fgw; a.F = F; a.foff = foff; a.Bs = Bs; a.s0 = s0; a.s1 = s1;
   a.hist = hist; a.n_slots = n_slots; a.wyy = wyy; a.bq = pack_bq; a.need = need; a.n_work_dev = n_work_dev;
+  a.lw = (lw == 2 && fgw % 8 == 0 && foff % 8 == 0 && Fp % 8 == 0) ? 2 : 1;
   switch (mode) {
-    case 0: if (vb) lq_pv<0, true>(posv, pack, lw, a); else lq_pv<0, false>(posv, pack, lw, a); break;
-    case 1: lq_pv<1, true>(posv, 0, lw, a); break;
-    default: if (vb) lq_pv<2, true>(posv, 0, lw, a); else lq_pv<2, false>(posv, 0, lw, a); break;
+    case 0: if (vb) lq_pv<0, true>(posv, pack, a); else lq_pv<0, false>(posv, pack, a); break;
+    case 1: lq_pv<1, true>(posv, 0, a); break;
+    default: if (vb) lq_pv<2, true>(posv, 0, a); else lq_pv<2, false>(posv, 0, a); break;
   }
   return (int)hipGetLastError();
 }
@@ -490,7 +471,7 @@ __device__ __forceinline__ unsigned long long fx_signed(float v, float s) {
 // slots 32..35 alias banks 0..3).  The bin-row pitch stays G.  F = 100: the
 // second group holds 36 features -> 9 lanes x 7 rows, 4 atomic instructions
 // per 7 rows where the full-width mapping issues 8 per 8 rows.  Bit-identical
-// histograms (integer LDS sums), measured slower: see g_bm_ragged below.
+// histograms (integer LDS sums), measured slower: see bm_tail below.
 template <int G, int CL, int MODE, bool HAS_VB, bool POSV, bool PACK, int LW, bool IDENT, bool RAG, bool MASK = false>
 __device__ __forceinline__ void hist_bm_body(
     const uint8_t* __restrict__ codes, int Fp, const int* __restrict__ ridx,
@@ -743,7 +724,7 @@ __global__ __launch_bounds__(1024) void hist_bm_kernel(
 static int g_bm_dbg = 0;
 extern "C" void h2o_hist_bm_set_debug(int flags) { g_bm_dbg = flags; }
 
-// Ragged last group (h2o_hist_bm_set_ragged): 0 = off (default); 1 = 4 codes
+// Ragged last group (h2o_hist_bm's `ragged`): 0 = off (default); 1 = 4 codes
 // per lane, slot stride 16; 2 = 4 codes per lane, slot stride = lanes per row;
 // 3 = 8 codes per lane, slot stride 8; 4 = the full-width mapping with the
 // atomics of the padding codes masked.  Off by default: every variant is
@@ -751,18 +732,16 @@ extern "C" void h2o_hist_bm_set_debug(int flags) { g_bm_dbg = flags; }
 // groups of a work item share each 128-B row through L2 only while they run
 // at the same pace, and a last group that runs ahead makes the other one
 // fetch the rows from HBM again.  Kept for frames and parts where that
-// changes.  A setter, not a static: tests flip it in one process.
-static int g_bm_ragged = 0;
-extern "C" void h2o_hist_bm_set_ragged(int mode) { g_bm_ragged = mode; }
-
+// changes.
+//
 // Mapping of the last group: codes-per-lane dwords (0: full width), lanes per row, slot stride.
 struct BmTail { int lw, lpr, ss; };
-static BmTail bm_tail(int F, int foff, int Fp, int G, int CL, int n_fg) {
+static BmTail bm_tail(int ragged, int F, int foff, int Fp, int G, int CL, int n_fg) {
   BmTail t{0, 0, 0};
   const int fg0 = foff + (n_fg - 1) * G, nf = F - fg0;
-  if (g_bm_ragged <= 0 || g_bm_ragged > 4 || G != 64 || CL != 1 || nf >= G) return t;
-  if (g_bm_ragged == 4) return BmTail{3, 0, 0};   // full-width lanes, padding atomics masked: decode unchanged
-  if (g_bm_ragged == 3) {
+  if (ragged <= 0 || ragged > 4 || G != 64 || CL != 1 || nf >= G) return t;
+  if (ragged == 4) return BmTail{3, 0, 0};   // full-width lanes, padding atomics masked: decode unchanged
+  if (ragged == 3) {
     const int l = (nf + 7) / 8;
     // 8 atomic instructions per 64/l rows beat the full width's 8 per 8 rows for l <= 7
     if (l <= 7 && fg0 + 8 * l <= Fp) return BmTail{2, l, 8};
@@ -770,7 +749,7 @@ static BmTail bm_tail(int F, int foff, int Fp, int G, int CL, int n_fg) {
   const int l = (nf + 3) / 4;
   // 4 atomic instructions per 64/l rows: no better than 1 per row above 12 lanes
   if (l > 12) return t;
-  return BmTail{1, l, g_bm_ragged == 2 ? l : 16};
+  return BmTail{1, l, ragged == 2 ? l : 16};
 }
 
 template <int G, int CL, int M, bool V, bool PV, bool PK, int LW, int TLW = 0, bool ID = false>
@@ -788,11 +767,11 @@ static int lbm_u(const QuadArgs& a) {
   return (int)hipGetLastError();
 }
 
-// H2O3_HIST_BM_LW: codes per lane (1 -> 4, 2 -> 8; A/B of the per-row work amortisation)
+// a.lw: codes per lane (1 -> 4, 2 -> 8; A/B of the per-row work amortisation);
+// h2o_hist_bm, the only caller, has made it 1 or 2, and 1 for G = 16
 // ID: no row ids (a.ridx == nullptr), the instances of the device tree's root
 template <int G, int CL, int M, bool V, bool PV, bool PK, bool ID>
 static int lbm_t(const QuadArgs& a) {
-  static const int lw = env_int("H2O3_HIST_BM_LW", 2);
   if constexpr (G == 64 && CL == 1) {
     // ragged last group: one more instance per tail width (h2o_hist_bm sets
     // t_lw only with the default 8 codes per lane in the full groups)
@@ -801,8 +780,7 @@ static int lbm_t(const QuadArgs& a) {
     if (a.t_lw == 3) return lbm_u<G, CL, M, V, PV, PK, 2, 3, ID>(a);
   }
   if constexpr (ID) return lbm_u<G, CL, M, V, PV, PK, 2, 0, true>(a);
-  // G = 16: 8 rows share a 16-lane group, too many for 4 byte rotations -> 4 codes per lane
-  return (lw == 1 || G == 16) ? lbm_u<G, CL, M, V, PV, PK, 1>(a) : lbm_u<G, CL, M, V, PV, PK, 2>(a);
+  return a.lw == 1 ? lbm_u<G, CL, M, V, PV, PK, 1>(a) : lbm_u<G, CL, M, V, PV, PK, 2>(a);
 }
 
 template <int G, int CL, int M, bool V, bool PV, bool PK>
@@ -904,10 +882,13 @@ __global__ __launch_bounds__(256) void hist_bm_reduce_kernel(
 // n_work_dev != nullptr: device-built work list (n_work = capacity).
 // part != nullptr: [n_work][n_fg][Bs][G*CL] u64 scratch for the two-pass
 // flush (partial images + hist_bm_reduce_kernel); nullptr: f64 atomic flush.
+// lw: code dwords per lane (1 or 2; G = 16 always runs 1); ragged: mapping of
+// a short last group (bm_tail), only with 8 codes per lane in the full groups.
 extern "C" int h2o_hist_bm(const void* codes, int Fp, const int* ridx, const float* va, const float* vb,
                            const int* work, int n_work, int F, int foff, int Bs, float s0, float s1,
                            double* hist, int n_slots, int mode, double* wyy, int posv, long long pack_bq, int G,
-                           const uint8_t* need, const int* n_work_dev, unsigned long long* part, hipStream_t s) {
+                           int lw, int ragged, const uint8_t* need, const int* n_work_dev,
+                           unsigned long long* part, hipStream_t s) {
   if (n_work <= 0 || foff >= F) return 0;
   if (Fp % 4 != 0 || foff % 4 != 0 || Bs > 256 || Bs % 4 != 0 || mode < 0 || mode > 2) return -1;
   const bool pack = pack_bq >= 0 && mode == 0;
@@ -923,9 +904,10 @@ extern "C" int h2o_hist_bm(const void* codes, int Fp, const int* ridx, const flo
   a.n_work = n_work; a.n_fg = n_fg; a.fgw = G; a.F = F; a.foff = foff; a.Bs = Bs; a.s0 = s0; a.s1 = s1;
   a.hist = hist; a.n_slots = n_slots; a.wyy = wyy; a.bq = pack_bq; a.need = need; a.n_work_dev = n_work_dev;
   a.part = part;
-  static const int lw_env = env_int("H2O3_HIST_BM_LW", 2);
-  const int lw = (lw_env == 1 || G == 16) ? 1 : 2;   // as lbm() picks it
-  const BmTail tail = lw == 2 ? bm_tail(F, foff, Fp, G, CL, n_fg) : BmTail{0, 0, 0};
+  // G = 16: 8 rows share a 16-lane group, too many for 4 byte rotations -> 4 codes per lane
+  lw = (lw == 1 || G == 16) ? 1 : 2;
+  a.lw = lw;
+  const BmTail tail = lw == 2 ? bm_tail(ragged, F, foff, Fp, G, CL, n_fg) : BmTail{0, 0, 0};
   // ridx == nullptr: row id = position (the root of a tree); one-channel G = 64
   // layouts with position-ordered payloads and 8 codes per lane only
   if (ridx == nullptr && !(G == 64 && CL == 1 && posv != 0 && lw == 2)) return -5;
@@ -1478,32 +1460,26 @@ int h2o_hist_build_pk(const void* codes, int code_bytes, int Fp, const int* ridx
                                0, threads, wyy, posv, need, s, bq);
 }
 
+// The partition / leaf wrappers h2o_part_flags, h2o_part_compact and
+// h2o_leaf_pos take a nullable `counts`: when set, the item count is read on
+// the device (counts[1]) and n_work is the launch capacity.
 int h2o_part_flags(const void* codes, int code_bytes, long long rs, long long fs, const int* ridx,
                    const int* work, const int* fbase, int n_work, const int* feat, const uint8_t* masks, int Bs,
-                   unsigned long long* flags, int* cnt, hipStream_t s) {
+                   unsigned long long* flags, int* cnt, const int* counts, hipStream_t s) {
   if (n_work <= 0) return 0;
   if (code_bytes == 1)
     hipLaunchKernelGGL(part_flags_kernel<uint8_t>, dim3(n_work), dim3(256), 0, s, (const uint8_t*)codes, rs, fs,
-                       ridx, (const int4*)work, fbase, feat, masks, Bs, flags, cnt, nullptr);
+                       ridx, (const int4*)work, fbase, feat, masks, Bs, flags, cnt, counts);
   else
     hipLaunchKernelGGL(part_flags_kernel<uint16_t>, dim3(n_work), dim3(256), 0, s, (const uint16_t*)codes, rs, fs,
-                       ridx, (const int4*)work, fbase, feat, masks, Bs, flags, cnt, nullptr);
+                       ridx, (const int4*)work, fbase, feat, masks, Bs, flags, cnt, counts);
   return (int)hipGetLastError();
 }
 
+// counts != nullptr: the pair count is read on the device (counts[0]); nb = capacity.
 int h2o_hist_sibling(const double* Hb, const double* Hp, const int* slots, int nb, int np, int nf, int F, int BsC,
                      int C, int clamp_mask, double* H, const double* wyy_b, const double* wyy_p, double* wyy_out,
-                     hipStream_t s) {
-  if (nb <= 0 || F <= 0) return 0;
-  hipLaunchKernelGGL(hist_sibling_kernel, dim3(nb, F), dim3(256), 0, s, Hb, Hp, slots, nb, np, nf, BsC, C, clamp_mask,
-                     H, wyy_b, wyy_p, wyy_out, nullptr);
-  return (int)hipGetLastError();
-}
-
-// Same with the pair count read on the device (counts[0]); nb = capacity.
-int h2o_hist_sibling_dev(const double* Hb, const double* Hp, const int* slots, int nb, int np, int nf, int F,
-                         int BsC, int C, int clamp_mask, double* H, const double* wyy_b, const double* wyy_p,
-                         double* wyy_out, const int* counts, hipStream_t s) {
+                     const int* counts, hipStream_t s) {
   if (nb <= 0 || F <= 0) return 0;
   hipLaunchKernelGGL(hist_sibling_kernel, dim3(nb, F), dim3(256), 0, s, Hb, Hp, slots, nb, np, nf, BsC, C, clamp_mask,
                      H, wyy_b, wyy_p, wyy_out, counts);
@@ -1601,15 +1577,10 @@ int h2o_part_offsets(const int* cnt, const long long* meta, int nw, int n, int* 
 
 int h2o_part_compact(const int* ridx, const int* work, const int* fbase, int n_work,
                      const unsigned long long* flags, const int* loff, const int* roff, int* out, const float* pa,
-                     float* pa_out, hipStream_t s) {
+                     float* pa_out, const int* counts, hipStream_t s) {
   if (n_work <= 0) return 0;
-  static const int cu = [] { const char* e = getenv("H2O3_PART_U"); return e ? atoi(e) : 4; }();
-  if (cu == 1)
-    hipLaunchKernelGGL(part_compact_kernel<1>, dim3(n_work), dim3(256), 0, s, ridx, (const int4*)work, fbase, flags,
-                       loff, roff, out, pa, pa_out, nullptr);
-  else
-    hipLaunchKernelGGL(part_compact_kernel<4>, dim3(n_work), dim3(256), 0, s, ridx, (const int4*)work, fbase, flags,
-                       loff, roff, out, pa, pa_out, nullptr);
+  hipLaunchKernelGGL(part_compact_kernel<4>, dim3(n_work), dim3(256), 0, s, ridx, (const int4*)work, fbase, flags,
+                     loff, roff, out, pa, pa_out, counts);
   return (int)hipGetLastError();
 }
 
@@ -1735,9 +1706,10 @@ extern "C" int h2o_seg_sum2(const int* ridx, const float* a, const float* b, con
   return (int)hipGetLastError();
 }
 
-extern "C" int h2o_leaf_pos(const float* zp, const int* work, int n_work, int mode, double* out, hipStream_t s) {
+extern "C" int h2o_leaf_pos(const float* zp, const int* work, int n_work, int mode, double* out, const int* counts,
+                            hipStream_t s) {
   if (n_work <= 0) return 0;
-  hipLaunchKernelGGL(leaf_pos_kernel, dim3(n_work), dim3(256), 0, s, zp, (const int4*)work, mode, out, nullptr);
+  hipLaunchKernelGGL(leaf_pos_kernel, dim3(n_work), dim3(256), 0, s, zp, (const int4*)work, mode, out, counts);
   return (int)hipGetLastError();
 }
 
@@ -1994,32 +1966,11 @@ static void pair_hist_multi_launch(bool has_vb, bool posv, int n_work, size_t ld
 
 // Grouped version of h2o_pair_hist: work[i].w bits 8..15 = pairs in the group
 // (<= 4, consecutive pairs of one node starting at work[i].x).
-static int pair_hist4_impl(const void* codes_col, int code_bytes, long long ncol, const int* ridx,
-                           const float* va, const float* vb, const int* work, int n_work, const int* pfeat,
-                           int Bs, int mode, int posv, float s0, float s1, double* Hp, double* pwyy,
-                           hipStream_t s, const int* fbins);
-
+// fbins != nullptr leaves each pair's bins [fbins[f], Bs - 1) unwritten.
 extern "C" int h2o_pair_hist4(const void* codes_col, int code_bytes, long long ncol, const int* ridx,
                               const float* va, const float* vb, const int* work, int n_work, const int* pfeat,
                               int Bs, int mode, int posv, float s0, float s1, double* Hp, double* pwyy,
-                              hipStream_t s) {
-  return pair_hist4_impl(codes_col, code_bytes, ncol, ridx, va, vb, work, n_work, pfeat, Bs, mode, posv, s0, s1,
-                         Hp, pwyy, s, nullptr);
-}
-
-// h2o_pair_hist4 that leaves each pair's bins [fbins[f], Bs - 1) unwritten.
-extern "C" int h2o_pair_hist4b(const void* codes_col, int code_bytes, long long ncol, const int* ridx,
-                               const float* va, const float* vb, const int* work, int n_work, const int* pfeat,
-                               int Bs, int mode, int posv, float s0, float s1, double* Hp, double* pwyy,
-                               hipStream_t s, const int* fbins) {
-  return pair_hist4_impl(codes_col, code_bytes, ncol, ridx, va, vb, work, n_work, pfeat, Bs, mode, posv, s0, s1,
-                         Hp, pwyy, s, fbins);
-}
-
-static int pair_hist4_impl(const void* codes_col, int code_bytes, long long ncol, const int* ridx,
-                           const float* va, const float* vb, const int* work, int n_work, const int* pfeat,
-                           int Bs, int mode, int posv, float s0, float s1, double* Hp, double* pwyy,
-                           hipStream_t s, const int* fbins) {
+                              const int* fbins, hipStream_t s) {
   if (n_work <= 0) return 0;
   if (Bs < 2 || Bs > 4096 || (mode != 0 && mode != 1) || (mode == 1 && vb == nullptr)) return -1;
   const size_t lds = (size_t)4 * Bs * 2 * sizeof(unsigned long long);
@@ -2741,37 +2692,7 @@ int h2o_dt_root_leaf_iota(const double* rec, int* ridx0, long long n, hipStream_
   return (int)hipGetLastError();
 }
 
-// The partition / leaf kernels with the item count read on the device
-// (counts[1]); n_cap = launch capacity.
-int h2o_part_flags_dev(const void* codes, int code_bytes, long long rs, long long fs, const int* ridx, const int* work,
-                       const int* fbase, int n_cap, const int* feat, const uint8_t* masks, int Bs,
-                       unsigned long long* flags, int* cnt, const int* counts, hipStream_t s) {
-  if (n_cap <= 0) return 0;
-  if (code_bytes == 1)
-    hipLaunchKernelGGL(part_flags_kernel<uint8_t>, dim3(n_cap), dim3(256), 0, s, (const uint8_t*)codes, rs, fs, ridx,
-                       (const int4*)work, fbase, feat, masks, Bs, flags, cnt, counts);
-  else
-    hipLaunchKernelGGL(part_flags_kernel<uint16_t>, dim3(n_cap), dim3(256), 0, s, (const uint16_t*)codes, rs, fs,
-                       ridx, (const int4*)work, fbase, feat, masks, Bs, flags, cnt, counts);
-  return (int)hipGetLastError();
-}
-
-int h2o_part_compact_dev(const int* ridx, const int* work, const int* fbase, int n_cap,
-                         const unsigned long long* flags, const int* loff, const int* roff, int* out, const float* pa,
-                         float* pa_out, const int* counts, hipStream_t s) {
-  if (n_cap <= 0) return 0;
-  hipLaunchKernelGGL(part_compact_kernel<4>, dim3(n_cap), dim3(256), 0, s, ridx, (const int4*)work, fbase, flags, loff,
-                     roff, out, pa, pa_out, counts);
-  return (int)hipGetLastError();
-}
-
-int h2o_leaf_pos_dev(const float* zp, const int* work, int n_cap, int mode, double* out, const int* counts,
-                     hipStream_t s) {
-  if (n_cap <= 0) return 0;
-  hipLaunchKernelGGL(leaf_pos_kernel, dim3(n_cap), dim3(256), 0, s, zp, (const int4*)work, mode, out, counts);
-  return (int)hipGetLastError();
-}
-
+// h2o_leaf_scatter with the item count read on the device (counts[1]); n_cap = launch capacity.
 int h2o_leaf_scatter_dev(const int* ridx, const int* work, int n_cap, const float* val, float* d, const int* counts,
                          hipStream_t s) {
   if (n_cap <= 0) return 0;

@@ -800,7 +800,7 @@ __global__ __launch_bounds__(256) void pair_select_kernel(const double* __restri
 template <int CRIT>
 static int pair_select_launch(int BP, int n, hipStream_t s, const double* Hp, int Bs, int kp, const double* res,
                               const int* pfeat, const unsigned char* fcat, double min_w2, int stride, double* pk,
-                              uint8_t* mask, int* feat_out, const int* fbins = nullptr) {
+                              uint8_t* mask, int* feat_out, const int* fbins) {
 #define PSK(bp)                                                                                                   \
   case bp:                                                                                                        \
     hipLaunchKernelGGL((pair_select_kernel<CRIT, bp>), dim3(n), dim3(256), 0, s, Hp, Bs, kp, res, pfeat, fcat, \
@@ -815,27 +815,11 @@ static int pair_select_launch(int BP, int n, hipStream_t s, const double* Hp, in
 
 // n nodes x kp pairs (node-major); Hp [n*kp][Bs][2] f64; res [n*kp][2]
 // (cat_pair_kernel output); pfeat [n*kp] global feature ids; fcat [F] u8.
+// fbins != nullptr: the pair histograms were written up to each feature's
+// bins only (fbins [F]: codes below the NA bin; h2o_pair_hist4 with fbins).
 extern "C" int h2o_pair_select(const double* Hp, int n, int Bs, int kp, const double* res, const int* pfeat,
                                const unsigned char* fcat, int crit, double min_w2, int stride, double* pk,
-                               uint8_t* mask, int* feat_out, hipStream_t s) {
-  if (n <= 0) return 0;
-  if (kp <= 0 || Bs < 3 || stride < 11) return -1;
-  int BP = 256;
-  while (BP < Bs - 1) BP <<= 1;
-  if (BP > 4096) return -2;
-  const int rc = crit == 1 ? pair_select_launch<1>(BP, n, s, Hp, Bs, kp, res, pfeat, fcat, min_w2, stride, pk, mask,
-                                                   feat_out)
-                           : pair_select_launch<0>(BP, n, s, Hp, Bs, kp, res, pfeat, fcat, min_w2, stride, pk, mask,
-                                                   feat_out);
-  if (rc) return rc;
-  return (int)hipGetLastError();
-}
-
-// h2o_pair_select for pair histograms written up to each feature's bins
-// (fbins [F]: codes below the NA bin; h2o_pair_hist4b).
-extern "C" int h2o_pair_select2(const double* Hp, int n, int Bs, int kp, const double* res, const int* pfeat,
-                                const unsigned char* fcat, int crit, double min_w2, int stride, double* pk,
-                                uint8_t* mask, int* feat_out, const int* fbins, hipStream_t s) {
+                               uint8_t* mask, int* feat_out, const int* fbins, hipStream_t s) {
   if (n <= 0) return 0;
   if (kp <= 0 || Bs < 3 || stride < 11) return -1;
   int BP = 256;

@@ -150,13 +150,6 @@ def bm_ragged() -> int:
     return int(env("H2O3_HIST_BM_RAGGED", "0"))
 
 
-def set_bm_ragged(lib, mode=None):
-    """Hand the switch to the library before a h2o_hist_bm launch
-    (launch_hist_bm, the one call site, does: the value of one caller never
-    leaks into another's)."""
-    lib.h2o_hist_bm_set_ragged(bm_ragged() if mode is None else int(mode))
-
-
 def channels(mode: int) -> int:
     """Histogram channels: 0 (w, w*y), 1 (g, h), 2 (w), 3 uplift (wt, wt*y, wc, wc*y)."""
     return 1 if mode == 2 else (4 if mode == 3 else 2)
@@ -323,6 +316,8 @@ class HistPlan(NamedTuple):
     threads: int    # workgroup size handed to the kernel (the bin-major kernel fixes its own)
     mode: int
     Bs: int
+    lw: int         # code dwords per lane asked of "bm" (H2O3_HIST_BM_LW) / "quad" (H2O3_HIST_LW); 0: "pk", "flat"
+    ragged: int     # bm_ragged(): lane mapping of a narrow last group of "bm"
 
     def scales(self, vmax):
         """(s0, s1, pack_bq): fixed-point scales of the two channels for channel
@@ -370,20 +365,25 @@ def hist_plan(bd, mode, unit_w, rows, target_blocks=None, quad_budget=_LDS_BUDGE
         pack = False
         kernel, n_fg, width = layout(False)
     threads = 0 if kernel == "bm" else quad_threads if kernel == "quad" else 512 if chunk >= 8192 else 256
-    return HistPlan(kernel, n_fg, width, pack, chunk, threads, mode, Bs)
+    # code dwords per lane asked of the one-byte-code kernels (A/B switches, read here and nowhere else),
+    # as 1 or 2: any other value means the kernel's default, as the library takes it
+    lw = 0
+    if kernel == "bm":
+        lw = 1 if int(env("H2O3_HIST_BM_LW", "2")) == 1 else 2
+    elif kernel == "quad":
+        lw = 2 if int(env("H2O3_HIST_LW", "1")) == 2 else 1
+    return HistPlan(kernel, n_fg, width, pack, chunk, threads, mode, Bs, lw, bm_ragged())
 
 
 def launch_hist_bm(lib, plan, bd, ridx, va, vb, work, n_work, scales, hist, n_slots, wyy, posv, part, need=None,
-                   cnts=None, ragged=None):
+                   cnts=None):
     """h2o_hist_bm from a plan: n_work work items (cnts: their device-side
     count, n_work then being the capacity) of `work` into hist [F, n_slots,
-    Bs, C]; the ragged-group switch is handed over first (`ragged`: a value
-    read earlier, e.g. before a graph capture)."""
-    set_bm_ragged(lib, ragged)
+    Bs, C]."""
     s0, s1, bq = scales
     rc = lib.h2o_hist_bm(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), n_work, bd.F, 0, bd.Bs,
                          s0, s1, _ptr(hist), n_slots, plan.mode, _ptr(wyy), 1 if posv else 0, bq, plan.width,
-                         _ptr(need), _ptr(cnts), _ptr(part), _stream())
+                         plan.lw, plan.ragged, _ptr(need), _ptr(cnts), _ptr(part), _stream())
     _check(rc, f"h2o_hist_bm (F={bd.F}, Fp={bd.Fp}, G={plan.width})")
 
 
@@ -438,10 +438,10 @@ def hist_build(bd, ridx, va, vb, mode, starts, counts, n_slots, use_native=None,
             launch_hist_bm(lib, plan, bd, ridx, va, vb, work, len(items), (s0, s1, bq), hist, n_slots, wyy, posv,
                            plan.part(len(items), dev), need=need)
         elif plan.kernel == "quad":
-            rc = lib.h2o_hist_quad3(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), len(items),
-                                    bd.F, 0, bd.Bs, s0, s1, _ptr(hist), n_slots, mode, plan.threads, _ptr(wyy), posv,
-                                    bq, plan.width, _ptr(need), _stream())
-            _check(rc, f"h2o_hist_quad3 (F={bd.F}, Fp={bd.Fp}, fgw={plan.width})")
+            rc = lib.h2o_hist_quad(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), len(items),
+                                   bd.F, 0, bd.Bs, s0, s1, _ptr(hist), n_slots, mode, plan.threads, _ptr(wyy), posv,
+                                   bq, plan.width, plan.lw, _ptr(need), None, _stream())
+            _check(rc, f"h2o_hist_quad (F={bd.F}, Fp={bd.Fp}, fgw={plan.width})")
         elif plan.kernel == "pk":
             _check(lib.h2o_hist_build_pk(_ptr(bd.codes), bd.code_bytes, bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb),
                                          _ptr(work), len(items), bd.F, plan.width, bd.Bs, s1, bq, _ptr(hist), n_slots,
@@ -636,15 +636,13 @@ def pair_hist_dev(bd, ridx, va, vb, mode, node_st, node_ct, sel, vmax, posv=Fals
     pwyy = torch.zeros(P, dtype=torch.float64, device=dev) if want_wyy else None
     if m:
         s0, s1 = (fixed_point_scale(v, min(chunk, int(ct.max()))) for v in vmax)
-        fn = lib.h2o_pair_hist4 if kp > 1 else lib.h2o_pair_hist
         args = [_ptr(bd.codes_col), bd.code_bytes, bd.codes_col.stride(0), _ptr(ridx), _ptr(va), _ptr(vb),
-                _ptr(items), n_items, _ptr(pfeat), Bs, mode, 1 if posv else 0, s0, s1, _ptr(Hp), _ptr(pwyy),
-                _stream()]
-        if kp > 1 and fbins is not None:
-            # bins past each feature's own codes stay unwritten (see h2o_pair_hist4b)
-            rc = lib.h2o_pair_hist4b(*args, _ptr(fbins))
+                _ptr(items), n_items, _ptr(pfeat), Bs, mode, 1 if posv else 0, s0, s1, _ptr(Hp), _ptr(pwyy)]
+        if kp > 1:
+            # with fbins, bins past each feature's own codes stay unwritten
+            rc = lib.h2o_pair_hist4(*args, _ptr(fbins), _stream())
         else:
-            rc = fn(*args)
+            rc = lib.h2o_pair_hist(*args, _stream())
         _check(rc, "h2o_pair_hist")
     return Hp, (pwyy.view(n, k)[:, 0].contiguous() if want_wyy else None), pfeat
 
@@ -705,7 +703,7 @@ def partition(bd, ridx, ridx_out, feats, masks, starts, counts, use_native=None,
             fbase = _h2d(fb_h, dev)
             flags = torch.empty(int(words.sum()) + 1, dtype=torch.int64, device=dev)
             rc = lib.h2o_part_flags(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), _ptr(fbase), nw,
-                                    _ptr(feat_t), _ptr(masks), bd.Bs, _ptr(flags), _ptr(cnt), _stream())
+                                    _ptr(feat_t), _ptr(masks), bd.Bs, _ptr(flags), _ptr(cnt), None, _stream())
         else:
             rc = lib.h2o_part_count(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), nw, _ptr(feat_t),
                                     _ptr(masks), bd.Bs, _ptr(cnt), _stream())
@@ -729,7 +727,7 @@ def partition(bd, ridx, ridx_out, feats, masks, starts, counts, use_native=None,
         pa, pb, pa_o, pb_o = payload if payload is not None else (None, None, None, None)
         if ballot:
             _check(lib.h2o_part_compact(_ptr(ridx), _ptr(work), _ptr(fbase), nw, _ptr(flags), _ptr(loff_d),
-                                        _ptr(roff_d), _ptr(ridx_out), _ptr(pa), _ptr(pa_o), _stream()),
+                                        _ptr(roff_d), _ptr(ridx_out), _ptr(pa), _ptr(pa_o), None, _stream()),
                    "h2o_part_compact")
             return nleft.tolist()
         _check(lib.h2o_part_scatter(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), nw, _ptr(feat_t),
@@ -836,7 +834,8 @@ def partition_async(bd, ridx, ridx_out, feat_d, masks, starts, counts, chunk=Non
         codes, rs, fs = bd.codes, bd.Fp, 1
     flags = torch.empty(total_words + 1, dtype=torch.int64, device=dev)
     _check(lib.h2o_part_flags(_ptr(codes), bd.code_bytes, rs, fs, _ptr(ridx), _ptr(work), _ptr(fbase), nw,
-                              _ptr(feat_t), _ptr(masks), bd.Bs, _ptr(flags), _ptr(cnt), _stream()), "h2o_part_flags")
+                              _ptr(feat_t), _ptr(masks), bd.Bs, _ptr(flags), _ptr(cnt), None, _stream()),
+           "h2o_part_flags")
     loff = torch.empty(nw, dtype=torch.int32, device=dev)
     roff = torch.empty(nw, dtype=torch.int32, device=dev)
     stride = pk.stride(0) if pk is not None else 0
@@ -844,7 +843,7 @@ def partition_async(bd, ridx, ridx_out, feat_d, masks, starts, counts, chunk=Non
                                 stride, pk_col, _stream()), "h2o_part_offsets")
     pa, _, pa_o, _ = payload if payload is not None else (None, None, None, None)
     _check(lib.h2o_part_compact(_ptr(ridx), _ptr(work), _ptr(fbase), nw, _ptr(flags), _ptr(loff), _ptr(roff),
-                                _ptr(ridx_out), _ptr(pa), _ptr(pa_o), _stream()), "h2o_part_compact")
+                                _ptr(ridx_out), _ptr(pa), _ptr(pa_o), None, _stream()), "h2o_part_compact")
     return nleft
 
 
@@ -890,9 +889,9 @@ def hist_build_dev(bd, ridx, va, vb, mode, rec, rec_cols, starts, counts, vmax, 
         launch_hist_bm(lib, plan, bd, ridx, va, vb, work, cap, (s0, s1, bq), Hb, n, wyy, posv, plan.part(cap, dev),
                        cnts=cnts)
         return Hb, wyy, slots, cnts
-    _check(lib.h2o_hist_quad4(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), cap, bd.F, 0, bd.Bs,
-                              s0, s1, _ptr(Hb), n, mode, plan.threads, _ptr(wyy), 1 if posv else 0, bq, plan.width,
-                              None, _ptr(cnts), _stream()), "h2o_hist_quad4")
+    _check(lib.h2o_hist_quad(_ptr(bd.codes), bd.Fp, _ptr(ridx), _ptr(va), _ptr(vb), _ptr(work), cap, bd.F, 0, bd.Bs,
+                             s0, s1, _ptr(Hb), n, mode, plan.threads, _ptr(wyy), 1 if posv else 0, bq, plan.width,
+                             plan.lw, None, _ptr(cnts), _stream()), "h2o_hist_quad")
     return Hb, wyy, slots, cnts
 
 
@@ -905,9 +904,9 @@ def hist_sibling_dev(Hb, H_prev, slots, cnts, clamp_mask, wyy_b=None, wyy_prev=N
     H = torch.empty((F, 2 * nb, Bs, C), dtype=Hb.dtype, device=Hb.device)
     wyy = torch.empty(2 * nb, dtype=torch.float64, device=Hb.device) if wyy_b is not None else None
     Hp = H_prev.contiguous()
-    _check(lib.h2o_hist_sibling_dev(_ptr(Hb), _ptr(Hp), _ptr(slots), nb, Hp.shape[1], 2 * nb, F, Bs * C, C, clamp_mask,
-                                    _ptr(H), _ptr(wyy_b), _ptr(wyy_prev), _ptr(wyy), _ptr(cnts), _stream()),
-           "h2o_hist_sibling_dev")
+    _check(lib.h2o_hist_sibling(_ptr(Hb), _ptr(Hp), _ptr(slots), nb, Hp.shape[1], 2 * nb, F, Bs * C, C, clamp_mask,
+                                _ptr(H), _ptr(wyy_b), _ptr(wyy_prev), _ptr(wyy), _ptr(cnts), _stream()),
+           "h2o_hist_sibling")
     return H, wyy
 
 
@@ -923,7 +922,7 @@ def hist_sibling(Hb, H_prev, build_slots, der_slots, par_slots, n_front, clamp_m
     Hb = Hb.contiguous()
     Hp = H_prev.contiguous()
     _check(lib.h2o_hist_sibling(_ptr(Hb), _ptr(Hp), _ptr(slots), nb, Hp.shape[1], n_front, F, Bs * C, C, clamp_mask,
-                                _ptr(H), _ptr(wyy_b), _ptr(wyy_prev), _ptr(wyy), _stream()), "h2o_hist_sibling")
+                                _ptr(H), _ptr(wyy_b), _ptr(wyy_prev), _ptr(wyy), None, _stream()), "h2o_hist_sibling")
     return H, wyy
 
 
@@ -1002,7 +1001,8 @@ def leaf_pos_sums(zpos, leaf_ids, starts, counts, n_leaves, mode, chunk=65536):
     items = make_work(starts, counts, leaf_ids, chunk)
     if len(items):
         work = _h2d(items, zpos.device)
-        _check(lib.h2o_leaf_pos(_ptr(zpos), _ptr(work), len(items), int(mode), _ptr(out), _stream()), "h2o_leaf_pos")
+        _check(lib.h2o_leaf_pos(_ptr(zpos), _ptr(work), len(items), int(mode), _ptr(out), None, _stream()),
+               "h2o_leaf_pos")
     return out
 
 

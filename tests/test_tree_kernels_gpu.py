@@ -360,7 +360,7 @@ def test_cat_pair_splits_match_dense_torch(crit):
 def test_packed_hist_group_widths_match_reference(fgw, lw, monkeypatch):
     """Packed single-atomic histogram at forced group widths (idle lanes when
     64 % lanes-per-row != 0, partial last group) vs the torch reference.
-    H2O3_HIST_LW is read once per process; both values give correct results."""
+    Both values of H2O3_HIST_LW give correct results."""
     _need_gpu()
     monkeypatch.setenv("H2O3_HIST_BM", "0")     # the grouped-lane kernel's widths
     monkeypatch.setenv("H2O3_HIST_FGW", fgw)
@@ -376,6 +376,37 @@ def test_packed_hist_group_widths_match_reference(fgw, lw, monkeypatch):
     h_gpu = tree_ops.hist_build(bd, ridx, va, vb, 0, starts, counts, 3, use_native=True, unit_w=True)
     h_ref = tree_ops.hist_build(bd, ridx, va, vb, 0, starts, counts, 3, use_native=False)
     torch.testing.assert_close(h_gpu, h_ref, rtol=1e-4, atol=1e-3)
+
+
+def test_quad_lw_paths_same_bits(monkeypatch):
+    """The grouped-lane kernel with 4 and with 8 codes per lane (H2O3_HIST_LW = 1,
+    2), both in this process, on a lone row, a partial wave and an odd-start
+    segment of three work items: the same histogram bits (packed entries are
+    integers times a power of two, so their f64 sums are exact in any order),
+    and each within the neighbouring test's tolerances of the torch reference."""
+    _need_gpu()
+    monkeypatch.setenv("H2O3_HIST_BM", "0")
+    monkeypatch.setenv("H2O3_HIST_FGW", "16")
+    from h2o3_amd.ops import tree_ops
+    bd, _ = _binned(n=6000, F=13, nbins=255, cats=False)
+    n = bd.nrows_local
+    starts, counts = [0, 1, 71], [1, 70, 5001]
+    # 8 codes per lane are honoured only for a group width and a row pitch that are multiples of 8
+    plan = tree_ops.hist_plan(bd, 0, True, sum(counts))
+    assert plan.kernel == "quad" and plan.pack and plan.width % 8 == 0 and bd.Fp % 8 == 0
+    assert -(-counts[2] // plan.chunk) == 3
+    g = torch.Generator(device="cuda").manual_seed(4)
+    ridx = torch.randperm(n, generator=g, device="cuda").to(torch.int32)
+    va = torch.randn(n, generator=g, device="cuda")
+    vb = (torch.rand(n, generator=g, device="cuda") < 0.7).to(torch.float32)
+    h_ref = tree_ops.hist_build(bd, ridx, va, vb, 0, starts, counts, 3, use_native=False)
+    h = {}
+    for lw in ("1", "2"):
+        monkeypatch.setenv("H2O3_HIST_LW", lw)
+        assert tree_ops.hist_plan(bd, 0, True, sum(counts)).lw == int(lw)
+        h[lw] = tree_ops.hist_build(bd, ridx, va, vb, 0, starts, counts, 3, use_native=True, unit_w=True)
+        torch.testing.assert_close(h[lw], h_ref, rtol=1e-4, atol=1e-3)
+    assert torch.equal(h["1"], h["2"])
 
 
 @pytest.mark.parametrize("sparse", [False, True])
@@ -904,9 +935,9 @@ def test_drf_pair_path_narrow_scoring_and_posv_same_trees(classify, monkeypatch)
 
 @pytest.mark.parametrize("weighted", [False, True])
 def test_pair_narrow_scoring_matches_torch_reference(weighted):
-    """The DRF device pair path with narrow bins (h2o_pair_hist4b leaves each
+    """The DRF device pair path with narrow bins (h2o_pair_hist4 with fbins leaves each
     pair's bins past its feature's own codes unwritten; cat_pair_kernel and
-    pair_select2 scan only [0, nbins_f) + NA) picks, per node, the gain,
+    h2o_pair_select scan only [0, nbins_f) + NA) picks, per node, the gain,
     feature and threshold of the torch split search (_find_splits_torch) run
     on the fp64 torch pair histograms of the same rows -- a 1000-level
     categorical makes Bs = 1025 while the numeric columns have <= 255 bins or
