@@ -56,9 +56,13 @@ from ...parallel import cloud
 from ...parallel import collectives as coll
 from ...utils import graphs
 from .engine import _TreeBuf
+from .record import FEAT, GAIN, OPT, T, rec_cols
 
+# the level record of the two-channel kernels (record.py), then this module's own columns
 RS = 16
-(GAIN, FEAT, T, OPT, L0, L1, R0, R1, T0, T1, OK, NL, NAW, ST, CT, VAL) = range(16)
+_RC = rec_cols(2)
+L0, L1, R0, R1, T0, T1, OK, NL, NAW = _RC.L, _RC.L + 1, _RC.R, _RC.R + 1, _RC.TOT, _RC.TOT + 1, _RC.OK, _RC.NL, _RC.NAW
+ST, CT, VAL = range(_RC.width, RS)
 MAX_DEPTH = 11
 
 

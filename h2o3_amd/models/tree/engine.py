@@ -31,8 +31,35 @@ from ...ops._native import check, ptr, stream
 from ...parallel import cloud
 from ...parallel import collectives as coll
 from ...utils.timer import phase
+from .record import decode, rec_cols, weight_col
 
 NEG_INF = float("-inf")
+
+
+def _row_weight(S, mode):
+    """Row weight of channel sums [..., C] (numpy or torch): the weight
+    channel, plus the control group's under uplift."""
+    return (S[:, 0] if mode != 1 else S[:, 1]) + (S[:, 2] if mode == 3 else 0.0)
+
+
+def _clamp_mask(mode):
+    """Channels a derived (parent minus built) sibling clamps at zero."""
+    return {0: 0b1, 1: 0b0}.get(mode, (1 << tree_ops.channels(mode)) - 1)
+
+
+@dataclass
+class _Frontier:
+    """The nodes of one level, in order (all share the depth)."""
+    id: np.ndarray                 # tree node ids
+    st: np.ndarray                 # row segments [st, st + ct) of ridx
+    ct: np.ndarray
+    tot: np.ndarray = None         # channel totals from the parent's split record (a last level builds no histograms)
+    allow: torch.Tensor = None     # [n, F] features the node may still split on (interaction constraints)
+    lo: np.ndarray = None          # monotone prediction bounds
+    hi: np.ndarray = None
+    p_build: np.ndarray = None     # of the node pairs: slot built from rows,
+    p_der: np.ndarray = None       # slot derived as parent minus built,
+    p_par: np.ndarray = None       # parent's slot in the previous level
 
 
 @dataclass
@@ -250,12 +277,6 @@ class TreeGrower:
         n = bd.nrows_local
         self.ridx = torch.empty(n, dtype=torch.int32, device=self.dev)
         self.ridx2 = torch.empty(n, dtype=torch.int32, device=self.dev)
-        # position-ordered copies of the two row channels, permuted with ridx
-        # (off by default: the extra scattered writes in the partition cost more
-        # than the contiguous histogram reads save — A/B in profiles/README.md)
-        self.use_payload = False
-        self._pay = [torch.empty(n, dtype=torch.float32, device=self.dev) for _ in range(4)] \
-            if self.use_payload else [None] * 4
         self.W = cloud.world()
         self.rank = cloud.rank()
         F = bd.F
@@ -269,8 +290,40 @@ class TreeGrower:
         self.rng = np.random.RandomState(params.seed & 0x7FFFFFFF)
         if tree_ops.env("H2O3_HIST_BUDGET"):
             params.hist_mem_budget = int(os.environ["H2O3_HIST_BUDGET"])
+        self.last_segs = None
+        # per tree (_start_tree): number of the tree being grown (the first is 0), histogram scale,
+        # the mode-0 response with 0/1 weights folded in as NaN and its [current, next] position-ordered
+        # copies, categorical mask rows in flight to _mask_stage, look-ahead histograms of the next level
+        self._tree_no = self._trees_grown = 0
+        self._adaptive = self._unit_w = False
+        self._stream_obj = self._vmax = self._va_eff = self._pos1 = self._mask_pend = self._la = self._last_wyy = None
+        # per level (_start_level)
+        self._level = self._depth = self._bnd_off = 0
+        self._bnd = self._adapt_par = self._adapt_next = self._rng_par = self._rng_cur = None
+        # lazy caches
+        self._elig_dev, self._ok_cache = {}, {}
+        self._ics_cache = self._qmask = self._is_cat_cpu = self._mono_f32 = self._nbins_t = None
+        self._fcat_u8 = self._pw_t = self._cutmat = self._mask_stage = None
+        self._d2h_ring, self._d2h_ev, self._d2h_k = [None, None], [None, None], 0
 
     # ------------------------------------------------------------------ hist
+    def _hist_response(self, va, vb, mode, moved=False):
+        """(va, vb, posv) a histogram kernel reads: the position-ordered
+        payload when the tree keeps one, else the NaN-masked response, else the
+        caller's channels.  moved=True reads the payload buffer the partition
+        just wrote (_pos1[1]: the look-ahead runs before the buffers swap)."""
+        if mode == 0 and self._pos1 is not None:
+            # moved by the partition compaction: read coalesced, no row gather
+            return self._pos1[1 if moved else 0], None, True
+        if mode == 0 and self._va_eff is not None:
+            return self._va_eff, None, False
+        return va, vb, False
+
+    def pos_payload(self):
+        """The mode-0 response of the last grown tree in position order (the
+        order of ridx), or None when the tree kept no such payload."""
+        return self._pos1[0] if self._pos1 is not None else None
+
     def _build_hist(self, ridx, va, vb, mode, starts, counts, need_mask=None):
         if mode == 3:
             # uplift: treatment and control (w, w*y) histograms side by side
@@ -281,23 +334,11 @@ class TreeGrower:
                                             vmax=self._vmax, posv=False, want_wyy=True)
             H = torch.cat([H1, H2], -1)
             self._last_wyy = None
-            if self.W > 1:
-                if self.Fpad > self.bd.F:
-                    H = torch.cat([H, torch.zeros((self.Fpad - self.bd.F,) + tuple(H.shape[1:]), dtype=H.dtype,
-                                                  device=H.device)], 0)
-                H = coll.reduce_scatter_dim0(H)
-            return H
-        posv = self.use_payload
-        if mode == 0 and getattr(self, "_pos1", None) is not None:
-            # NaN-masked responses kept in POSITION order (moved by the partition
-            # compaction): the histogram reads them coalesced, no row gather
-            va, vb, posv = self._pos1[0], None, True
-        elif mode == 0 and getattr(self, "_va_eff", None) is not None:
-            va, vb = self._va_eff, None   # 0/1 weights folded into NaN-masked responses
-        with phase("tree.hist"), phase(f"tree.hist.L{getattr(self, '_level', 0)}"):
+            return self._rs_hist_wyy(H, None)[0] if self.W > 1 else H
+        va, vb, posv = self._hist_response(va, vb, mode)
+        with phase("tree.hist"), phase(f"tree.hist.L{self._level}"):
             H, wyy = tree_ops.hist_build(self.bd, ridx, va, vb, mode, starts, counts, len(starts), vmax=self._vmax,
-                                         posv=posv, want_wyy=True,
-                                         unit_w=getattr(self, "_unit_w", False), need_mask=need_mask)
+                                         posv=posv, want_wyy=True, unit_w=self._unit_w, need_mask=need_mask)
         if self.W > 1:
             H, wyy = self._rs_hist_wyy(H, wyy)
         self._last_wyy = wyy
@@ -346,20 +387,15 @@ class TreeGrower:
         p = self.p
         F = self.bd.F
         base = np.ones(F, dtype=bool) if p.tree_col_mask is None else p.tree_col_mask.astype(bool)
-        rate = p.col_sample_rate * (p.col_sample_rate_change_per_level ** depth)
-        k = None
-        if p.mtries is not None and p.mtries > 0:
-            k = p.mtries
-        elif rate < 1.0:
-            k = max(1, int(math.floor(rate * base.sum() + 0.5)))
-        if k is None or k >= base.sum():
+        k, n_elig = self._sample_k(depth)
+        if k >= n_elig:
             return None
         elig = np.nonzero(base)[0]
         if self.dev.type == "cuda":
             # one HIP launch: per-node selection sampling, rows come out sorted
             # (was rand + top-k + gather + segmented sort, with a host sync)
             seed = int(self.rng.randint(0, 2 ** 31 - 1))
-            el = self.__dict__.setdefault("_elig_dev", {})
+            el = self._elig_dev
             key = elig.tobytes()
             if key not in el:
                 el.clear()
@@ -439,9 +475,8 @@ class TreeGrower:
         if not sets:
             return None
         F = self.bd.F
-        cached = self.__dict__.get("_ics_cache")
-        if cached is not None:
-            return cached
+        if self._ics_cache is not None:
+            return self._ics_cache
         allow = np.zeros((F, F), dtype=bool)
         root = np.zeros(F, dtype=bool)
         for st in sets:
@@ -456,11 +491,9 @@ class TreeGrower:
     def _bnd_dev(self, n):
         """[n, 2] f64 (lo, hi) prediction bounds of the frontier nodes being
         scored, or None when no node is bounded."""
-        b = getattr(self, "_bnd", None)
-        if b is None:
+        if self._bnd is None:
             return None
-        off = getattr(self, "_bnd_off", 0)
-        return b[off:off + n]
+        return self._bnd[self._bnd_off:self._bnd_off + n]
 
     def _bound_cost(self, Lb, Rb, lo, hi):
         """(gain penalty of clamping the children's constants into [lo, hi],
@@ -522,7 +555,7 @@ class TreeGrower:
         SharedTreeModel.java:59) tree by tree."""
         ht = getattr(self.bd, "hist_type", "auto")
         if ht == "roundrobin":
-            return self._RR_TYPES[(int(self.p.seed) + getattr(self, "_tree_no", 0)) % 4]
+            return self._RR_TYPES[(int(self.p.seed) + self._tree_no) % 4]
         return ht
 
     def _adapt_hist(self, H):
@@ -545,7 +578,7 @@ class TreeGrower:
             return H
         Fl, n, Bs, C = H.shape
         B = Bs - 1
-        depth = getattr(self, "_depth", 0)
+        depth = self._depth
         # bins per node: nbins_top_level at the root AND its children, halved per
         # level below (the reference fixture's splits, gbm_variable_importance.zip,
         # sit on 1024 / 512 / 256 / 128 cells of the parent's range at depths 1-4)
@@ -574,14 +607,14 @@ class TreeGrower:
             # per (tree, level, node, feature, bin) uniform draw: keep ~nb - 1 cuts
             key = (torch.arange(Fl, device=dev).view(-1, 1, 1) + f0) * 1000003 + \
                 torch.arange(n, device=dev).view(1, -1, 1) * 7919 + idx.view(1, 1, -1) * 104729 + \
-                (int(self.p.seed) * 31 + getattr(self, "_tree_no", 0) * 131 + depth * 17)
+                (int(self.p.seed) * 31 + self._tree_no * 131 + depth * 17)
             key = (key * 0x9E3779B1) & 0xFFFFFFFF
             key = ((key ^ (key >> 15)) * 0x2C1B3C6D) & 0xFFFFFFFF
             u = (key ^ (key >> 12)).to(torch.float64) / 4294967296.0
             pk = ((nb - 1) / (L - 1).clamp(min=1).to(torch.float64))
             is_end = inr & ((u < pk) | (idx == last))
         else:
-            qm = self.__dict__.get("_qmask")
+            qm = self._qmask
             if qm is None:
                 qm = torch.zeros((self.Fpad, B), dtype=torch.bool, device=dev)
                 for j, qb in enumerate(self.bd.qbounds or []):
@@ -631,8 +664,8 @@ class TreeGrower:
         occupied range is recorded for its children; without a parent record
         (root, chunk / frontier shapes that do not line up) the node's own
         range is used."""
-        off = getattr(self, "_bnd_off", 0)
-        cur = self.__dict__.get("_rng_cur")
+        off = self._bnd_off
+        cur = self._rng_cur
         n_level = off + n if cur is None or off == 0 else max(cur[0].shape[1], off + n)
         if cur is None or off == 0 or cur[0].shape[1] < n_level:
             nf = torch.zeros((Fl, n_level, 1), dtype=first.dtype, device=first.device)
@@ -642,8 +675,8 @@ class TreeGrower:
                 nf[:, :k], nl[:, :k] = cur[0][:, :k], cur[1][:, :k]
             cur = self._rng_cur = (nf, nl)
         cur[0][:, off:off + n], cur[1][:, off:off + n] = first, last
-        par = self.__dict__.get("_adapt_par")
-        rp = self.__dict__.get("_rng_par")
+        par = self._adapt_par
+        rp = self._rng_par
         if depth == 0 or par is None or rp is None or rp[0].shape[0] != Fl:
             return first, last
         sids, fs, ts, opts, n_front = par
@@ -687,7 +720,7 @@ class TreeGrower:
             return self._find_splits_torch(H, col_mask, node_wyy)
         Fl = H.shape[0]
         fsl = slice(self.f0, self.f0 + Fl)
-        if getattr(self, "_is_cat_cpu", None) is None:
+        if self._is_cat_cpu is None:
             self._is_cat_cpu = self.is_cat_t[fsl].cpu()
         is_cat = self._is_cat_cpu
         if bool(is_cat.all()):
@@ -724,16 +757,15 @@ class TreeGrower:
         cm = col_mask[:, fsl]
         if getattr(col_mask, "_all_true", False) and self.f0 + Fl <= self.bd.F:
             # no column sampling: a cached device mask of ones per frontier size
-            cache = self.__dict__.setdefault("_ok_cache", {})
-            ok = cache.get(n)
+            ok = self._ok_cache.get(n)
             if ok is None:
-                ok = cache[n] = torch.ones((n, Fl), dtype=torch.uint8, device=self.dev)
+                ok = self._ok_cache[n] = torch.ones((n, Fl), dtype=torch.uint8, device=self.dev)
         else:
             ok = cm.to(torch.uint8).contiguous()
             ok = tree_ops._h2d(ok.numpy(), self.dev) if ok.device.type == "cpu" else ok
             if self.f0 + Fl > self.bd.F:
                 ok[:, max(0, self.bd.F - self.f0):] = 0
-        if getattr(self, "_mono_f32", None) is None:
+        if self._mono_f32 is None:
             self._mono_f32 = self.mono_t[fsl].to(torch.float32).contiguous()
         mono = self._mono_f32
         H = H.contiguous()
@@ -869,10 +901,9 @@ class TreeGrower:
         """Collect the categorical mask rows of the previous level from the
         pinned staging buffer into the tree (waits on the copy's event: by the
         time the next level's record arrived it has completed)."""
-        pend = self.__dict__.get("_mask_pend")
-        if pend is None:
+        if self._mask_pend is None:
             return
-        nodes, feats, shape, ev = pend
+        nodes, feats, shape, ev = self._mask_pend
         ev.synchronize()
         n = int(np.prod(shape))
         tb.cat_parts.append((nodes, feats, self._mask_stage[:n].numpy().reshape(shape).copy()))
@@ -884,7 +915,7 @@ class TreeGrower:
         bins: H2O3_PAIR_NARROW), else None."""
         if self.dev.type != "cuda" or self.bd.Bs - 1 <= 256 or tree_ops.env("H2O3_PAIR_NARROW", "1") != "1":
             return None
-        if getattr(self, "_nbins_t", None) is None:
+        if self._nbins_t is None:
             nb = np.minimum(np.asarray(self.bd.nbins[:self.bd.F], dtype=np.int64), self.bd.Bs - 1)
             self._nbins_t = torch.as_tensor(nb.astype(np.int32), device=self.dev)
         return self._nbins_t
@@ -915,11 +946,7 @@ class TreeGrower:
         bd, dev = self.bd, self.dev
         F, Bs, C = bd.F, bd.Bs, 2
         n = len(f_st)
-        posv = False
-        if mode == 0 and getattr(self, "_pos1", None) is not None:
-            va, vb, posv = self._pos1[0], None, True
-        elif mode == 0 and getattr(self, "_va_eff", None) is not None:
-            va, vb = self._va_eff, None
+        va, vb, posv = self._hist_response(va, vb, mode)
         st = np.asarray(f_st, dtype=np.int64)
         ct = np.asarray(f_ct, dtype=np.int64)
         nz = torch.nonzero(cm[:, :F]).cpu().numpy()           # node-major pairs
@@ -955,13 +982,9 @@ class TreeGrower:
             elig = torch.as_tensor(np.nonzero(base)[0], device=dev)
             sel = elig.view(1, -1).expand(len(f_st), -1)
         n, k = sel.shape
-        posv = False
-        if mode == 0 and getattr(self, "_pos1", None) is not None:
-            va, vb, posv = self._pos1[0], None, True
-        elif mode == 0 and getattr(self, "_va_eff", None) is not None:
-            va, vb = self._va_eff, None
+        va, vb, posv = self._hist_response(va, vb, mode)
         lib = _native.get_lib("tree_split")
-        if getattr(self, "_fcat_u8", None) is None:
+        if self._fcat_u8 is None:
             self._fcat_u8 = self.is_cat_t[:bd.F].to(torch.uint8).contiguous()
         st = np.asarray(f_st, dtype=np.int64)
         ct = np.asarray(f_ct, dtype=np.int64)
@@ -1035,7 +1058,7 @@ class TreeGrower:
         dev = Hp.device
         P, Bs, C = Hp.shape
         nl = -(-n // W)
-        if getattr(self, "_pw_t", None) is None or self._pw_t.device != dev:
+        if self._pw_t is None or self._pw_t.device != dev:
             nb = np.minimum(np.asarray(self.bd.nbins[:self.bd.F], dtype=np.int64), Bs - 1) + 1
             self._pw_t = torch.as_tensor(nb, device=dev)
         w = self._pw_t[pf]
@@ -1567,8 +1590,8 @@ class TreeGrower:
     def pos_payload_ok(self):
         """True when grow() keeps the 0/1-weighted mode-0 response as a
         position-ordered NaN-masked payload (quad histogram kernels)."""
-        return self.dev.type == "cuda" and not self.use_payload and self.bd.code_bytes == 1 and \
-            self.bd.Bs <= 256 and self.bd.Fp % 16 == 0 and tree_ops.env("H2O3_HIST_KERNEL", "quad") == "quad" \
+        return self.dev.type == "cuda" and self.bd.code_bytes == 1 and self.bd.Bs <= 256 \
+            and self.bd.Fp % 16 == 0 and tree_ops.env("H2O3_HIST_KERNEL", "quad") == "quad" \
             and tree_ops.env("H2O3_POSV", "1") == "1" and tree_ops.env("H2O3_PART", "ballot") == "ballot"
 
     def grow(self, va, vb, mode, tree_node_hook=None, want_nid=True, vmax=None, unit_w=None, va_scratch=False):
@@ -1586,17 +1609,127 @@ class TreeGrower:
         bd, p = self.bd, self.p
         N = bd.nrows_local
         C = tree_ops.channels(mode)
-        self._tree_no = getattr(self, "_tree_no", -1) + 1
-        self._adaptive = getattr(bd, "hist_type", "auto") in ("uniformadaptive", "random", "roundrobin")
-        self._stream_obj = torch.cuda.current_stream() if self.dev.type == "cuda" else None
-        if not (self.dev.type == "cuda" and tree_ops.iota_i32(self.ridx)):
-            torch.arange(N, dtype=torch.int32, device=self.dev, out=self.ridx)
-        if self.dev.type != "cuda":
+        self._start_tree(va, vb, mode, vmax, unit_w, va_scratch)
+        tb = _TreeBuf()
+        # interaction constraints (GlobalInteractionConstraints /
+        # BranchInteractionConstraints): the features each frontier node may
+        # still split on; the root may use every feature named in a set
+        ics = self._interaction_map()
+        ics_t = torch.as_tensor(ics[0], device=self.dev) if ics is not None else None
+        # monotone node prediction bounds (Constraints._min / _max), per frontier node
+        mono_b = p.monotone is not None and bool(np.any(np.asarray(p.monotone) != 0))
+        fr = _Frontier(id=np.zeros(1, dtype=np.int64), st=np.zeros(1, dtype=np.int64), ct=np.full(1, N, dtype=np.int64),
+                       allow=torch.as_tensor(ics[1][None, :].copy(), device=self.dev) if ics is not None else None,
+                       lo=np.full(1, -np.inf) if mono_b else None, hi=np.full(1, np.inf) if mono_b else None)
+        H_prev = wyy_prev = wyy_level = None
+        leaf_parts = []    # per level: (node ids, starts, counts, totals [k, C])
+        # the whole frontier is partitioned on the device before the host reads the level record
+        part_dev = self.dev.type == "cuda" and not p.max_leaves and \
+            tree_ops.env("H2O3_ASYNC_PART", "1") == "1" and tree_ops.env("H2O3_PART", "ballot") == "ballot"
+        is_cat_np = np.asarray(bd.is_cat, dtype=bool)
+        depth = 0
+        coll._TAG.append("tree.L0")
+        ntag = len(coll._TAG)
+        while fr.id.size:
+            coll._TAG[ntag - 1] = f"tree.L{depth}"       # collective bytes per level (coll.bytes_report)
+            n_front = int(fr.id.size)
+            can_split = depth < p.max_depth
+            level_bytes = self.Fpad * n_front * bd.Bs * C * 8
+            prev_bytes = 0 if H_prev is None else H_prev.numel() * 8
+            chunked = can_split and (level_bytes + prev_bytes) > p.hist_mem_budget and n_front > 1
+            self._start_level(fr, depth)
+            direct = can_split and fr.allow is None and not self._adaptive and not mono_b and \
+                self._direct_level(mode, depth, chunked)
+            chunked = chunked or direct
+            la, self._la = self._la, None
+            if la is not None and (chunked or not can_split or la[0].shape[1] < n_front):
+                la = None   # defensive: the look-ahead only matches a full next level
+            if chunked:
+                # frontier too wide for one level of histograms, or column-sampled
+                # levels on the pair path: no parent level kept (no subtraction)
+                H, H_prev, wyy_level = None, None, None
+            elif not can_split and depth > 0:
+                # last level: no histograms needed, leaf totals come from the parent split stats
+                H = None
+            else:
+                H, wyy_level = self._level_hist(fr, va, vb, mode, depth, la, H_prev, wyy_prev, wyy_level)
+            if can_split:
+                sp = self._level_splits(fr, va, vb, mode, depth, H, wyy_level, direct, chunked, want_pk=part_dev)
+                dec = self._level_record(sp, fr, tb, va, vb, mode, depth, H, wyy_level, level_bytes, chunked, part_dev)
+                tots = dec.tot
+            else:
+                dec = None
+                tots = self._totals(H).numpy() if H is not None else fr.tot
+            tots = np.asarray(tots, dtype=np.float64)
+            w_a = _row_weight(tots, mode)
+            tb.weight[fr.id] = w_a
+            if dec is None:
+                ok = np.zeros(n_front, dtype=bool)
+            elif dec.ok is not None:
+                ok = dec.ok
+            else:
+                ok = np.isfinite(dec.gain)
+                if p.criterion != "xgb":
+                    ok &= w_a >= 2 * p.min_rows
+            if p.max_leaves:
+                self._leaf_budget(ok, dec.gain if dec is not None else None, sum(q[0].size for q in leaf_parts))
+            lf = ~ok
+            if lf.any():
+                leaf_parts.append((fr.id[lf], fr.st[lf], fr.ct[lf], tots[lf]))
+            sids = np.nonzero(ok)[0]
+            if sids.size == 0:
+                if dec is not None and dec.nleft is not None:
+                    self._swap_rows()   # the (identity) partition already ran
+                break
+            nid_s, f_s, Lsel, Rsel = fr.id[sids], dec.feat[sids], dec.L[sids], dec.R[sids]
+            cat_s = is_cat_np[f_s]
+            wl_a, wr_a = _row_weight(Lsel, mode), _row_weight(Rsel, mode)
+            lid = self._write_splits(tb, nid_s, depth, dec, sids, f_s, cat_s, Lsel, Rsel, wl_a, wr_a)
+            masks = None
+            if cat_s.any() or dec.nleft is None:
+                masks = sp["mask"] if sids.size == n_front else sp["mask"][tree_ops._h2d(sids, sp["mask"].device)]
+            if cat_s.any():
+                self._stage_cat_masks(tb, masks, nid_s, f_s, cat_s)
+            if dec.nleft is not None:
+                nleft = dec.nleft[sids]
+            else:
+                nleft = self._partition_sync(f_s, masks, fr.st[sids], fr.ct[sids])
+            self._swap_rows()
+            fr, H_prev, wyy_prev = self._next_frontier(fr, sids, lid, nleft, f_s, cat_s, Lsel, Rsel, wl_a <= wr_a,
+                                                       ics_t, mode, H, wyy_level)
+            depth += 1
+        del coll._TAG[ntag - 1:]
+        self._flush_masks(tb)
+        tree = tb.to_tree()
+        if leaf_parts:
+            leaf_ids, leaf_st, leaf_ct, leaf_tot_np = (np.concatenate(q, 0) for q in zip(*leaf_parts))
+        else:
+            leaf_ids = leaf_st = leaf_ct = np.zeros(0, dtype=np.int64)
+            leaf_tot_np = np.zeros((0, C))
+        leaves = leaf_ids.tolist()
+        nid = None
+        if want_nid:
+            with phase("tree.nid"):
+                nid = tree_ops.fill_nid(self.ridx, np.arange(len(leaves), dtype=np.int64), leaf_st, leaf_ct, N)
+        self.last_segs = (list(range(len(leaves))), leaf_st.tolist(), leaf_ct.tolist())
+        leaf_tot_t = torch.from_numpy(np.ascontiguousarray(leaf_tot_np, dtype=np.float64))
+        return tree, nid, leaves, leaf_tot_t
+
+    def _start_tree(self, va, vb, mode, vmax, unit_w, va_scratch):
+        """Per-tree state: identity row order, histogram scale, the form of the mode-0 response."""
+        on_dev = self.dev.type == "cuda"
+        self._tree_no = self._trees_grown
+        self._trees_grown += 1
+        self._adaptive = getattr(self.bd, "hist_type", "auto") in ("uniformadaptive", "random", "roundrobin")
+        self._stream_obj = torch.cuda.current_stream() if on_dev else None
+        if not (on_dev and tree_ops.iota_i32(self.ridx)):
+            torch.arange(self.bd.nrows_local, dtype=torch.int32, device=self.dev, out=self.ridx)
+        if not on_dev:
             self._vmax = None
         else:
             self._vmax = list(vmax) if vmax is not None else tree_ops.channel_max(va, vb, mode)
         # 0/1 row weights (unweighted data, row sampling) -> packed histogram atomics
-        self._unit_w = mode == 0 and self.dev.type == "cuda" and (
+        self._unit_w = mode == 0 and on_dev and (
             vb is None or (bool(unit_w) if unit_w is not None else bool(((vb == 0) | (vb == 1)).all())))
         self._va_eff = None
         quad = self.bd.code_bytes == 1 and self.bd.Bs <= 256 and self.bd.Fp % 16 == 0 and \
@@ -1604,430 +1737,287 @@ class TreeGrower:
         # every level on the row-direct pair path (DRF's mtries << F): the
         # pair kernels read the position-ordered payload at any histogram width
         all_direct = self._all_levels_direct(mode) and tree_ops.env("H2O3_DRF_POSV", "1") == "1"
-        if self._unit_w and not self.use_payload and (quad or all_direct):
+        if self._unit_w and (quad or all_direct):
             self._va_eff = torch.where(vb > 0, va, torch.full_like(va, float("nan"))) if vb is not None else va
         self._pos1 = None
         self._mask_pend = None
+        self._la = None
         if self._va_eff is not None and tree_ops.env("H2O3_POSV", "1") == "1" and \
                 tree_ops.env("H2O3_PART", "ballot") == "ballot":
             # va_scratch: the caller hands over va (a NaN-masked residual it
             # will not read again) as the root payload -- no copy
             p0 = self._va_eff.clone() if (self._va_eff is va and not va_scratch) else self._va_eff
             self._pos1 = [p0, torch.empty_like(p0)]   # root: position order == row order
-        ridx, ridx2 = self.ridx, self.ridx2
-        self._la = None
-        pa, pb, pa2, pb2 = self._pay
-        if self.use_payload:
-            pa.copy_(va)
-            if vb is not None:
-                pb.copy_(vb)
-            else:
-                pb.fill_(1.0)
-            va, vb = pa, pb   # position order == row order while ridx is the identity
-        tb = _TreeBuf()
-        # frontier as arrays (all nodes of a level share the depth): node ids,
-        # row segments [st, st + ct) of ridx, channel totals from the parent's
-        # split record (used when the last level builds no histograms)
-        f_id = np.zeros(1, dtype=np.int64)
-        f_st = np.zeros(1, dtype=np.int64)
-        f_ct = np.full(1, N, dtype=np.int64)
-        f_tot = None
-        depth = 0
-        H_prev = None
-        wyy_prev, wyy_level = None, None
-        # (build slot, derived slot, parent slot) of the node pairs of this level
-        p_build = p_der = p_par = None
-        leaf_parts = []    # per level: (node ids, starts, counts, totals [k, C])
-        level = 0
-        async_part = self.dev.type == "cuda" and not p.max_leaves and not self.use_payload and \
-            tree_ops.env("H2O3_ASYNC_PART", "1") == "1" and tree_ops.env("H2O3_PART", "ballot") == "ballot"
-        is_cat_np = np.asarray(bd.is_cat, dtype=bool)
-        # interaction constraints (GlobalInteractionConstraints /
-        # BranchInteractionConstraints): the features each frontier node may
-        # still split on; the root may use every feature named in a set
-        ics = self._interaction_map()
-        f_allow = torch.as_tensor(ics[1][None, :].copy(), device=self.dev) if ics is not None else None
-        ics_t = torch.as_tensor(ics[0], device=self.dev) if ics is not None else None
-        cutmat = self._cut_matrix()
-        # monotone node prediction bounds (Constraints._min / _max), per frontier node
-        mono_b = p.monotone is not None and bool(np.any(np.asarray(p.monotone) != 0))
-        f_lo = np.full(1, -np.inf) if mono_b else None
-        f_hi = np.full(1, np.inf) if mono_b else None
-        self._bnd, self._bnd_off = None, 0
 
-        coll._TAG.append("tree.L0")
-        ntag = len(coll._TAG)
-        while f_id.size:
-            self._level = level
-            coll._TAG[ntag - 1] = f"tree.L{level}"       # collective bytes per level (coll.bytes_report)
-            n_front = int(f_id.size)
-            can_split = depth < p.max_depth
-            C_ = tree_ops.channels(mode)
-            level_bytes = self.Fpad * n_front * bd.Bs * C_ * 8
-            prev_bytes = 0 if H_prev is None else H_prev.numel() * 8
-            chunked = can_split and (level_bytes + prev_bytes) > p.hist_mem_budget and n_front > 1
-            self._depth = depth
-            # parent records for the per-node adaptive ranges (_adapt_range)
-            nxt = self.__dict__.get("_adapt_next")
-            self._adapt_par = None if (depth == 0 or nxt is None) else nxt + (n_front,)
-            self._rng_par = None if depth == 0 else self.__dict__.get("_rng_cur")
-            self._rng_cur = None
-            self._adapt_next = None
-            direct = can_split and f_allow is None and not self._adaptive and not mono_b and \
-                self._direct_level(mode, depth, chunked)
-            if mono_b and bool(np.isfinite(f_lo).any() | np.isfinite(f_hi).any()):
-                self._bnd = torch.as_tensor(np.stack([f_lo, f_hi], 1), dtype=torch.float64, device=self.dev)
-            else:
-                self._bnd = None
-            self._bnd_off = 0
-            chunked = chunked or direct
-            la, self._la = self._la, None
-            if la is not None and (chunked or not can_split or la[0].shape[1] < n_front):
-                la = None   # defensive: the look-ahead only matches a full next level
-            if la is not None:
-                # this level's histograms were built on the device before the
-                # host read the previous level's decisions (_lookahead)
-                H = la[0][:, :n_front].contiguous()
-                wyy_level = la[1][:n_front] if la[1] is not None else None
-                if tree_ops.env("H2O3_LA_CHECK") == "1":
-                    self._la_check(la, p_build, p_der, p_par)
-            elif chunked:
-                # frontier too wide for one level of histograms, or column-sampled
-                # levels on the pair path: no parent level kept (no subtraction)
-                H, H_prev, wyy_level = None, None, None
-            elif not can_split and level > 0:
-                # last level: no histograms needed, leaf totals come from the parent split stats
-                H = None
-            elif level == 0 or H_prev is None:
-                H = self._build_hist(ridx, va, vb, mode, f_st, f_ct)
-                wyy_level = self._last_wyy
-            else:
-                Hb = self._build_hist(ridx, va, vb, mode, f_st[p_build], f_ct[p_build])
-            if la is not None:
-                pass
-            elif level > 0 and H_prev is not None and (can_split or level == 0) and self.dev.type == "cuda":
-                # copy + parent-minus-built subtraction in one kernel
-                clamp = {0: 0b1, 1: 0b0}.get(mode, (1 << tree_ops.channels(mode)) - 1)
-                wb = self._last_wyy if mode == 0 else None
-                H, wyy_n = tree_ops.hist_sibling(Hb, H_prev, p_build, p_der, p_par, n_front, clamp,
-                                                 wyy_b=wb, wyy_prev=wyy_prev if wb is not None else None)
-                if wyy_n is not None:
-                    wyy_level = wyy_n
-                del Hb
-            elif level > 0 and H_prev is not None and can_split:
-                H = torch.empty((Hb.shape[0], n_front) + tuple(Hb.shape[2:]), dtype=Hb.dtype, device=Hb.device)
-                bs = torch.as_tensor(p_build, device=Hb.device)
-                ds = torch.as_tensor(p_der, device=Hb.device)
-                ps = torch.as_tensor(p_par, device=Hb.device)
-                H[:, bs] = Hb
-                H[:, ds] = (H_prev[:, ps] - Hb).clamp_min_(0) if mode != 1 else (H_prev[:, ps] - Hb)
-                if mode == 0 and self._last_wyy is not None:
-                    wyy_level = torch.empty(n_front, dtype=torch.float64, device=Hb.device)
-                    wyy_level[bs] = self._last_wyy
-                    wyy_level[ds] = wyy_prev[ps] - self._last_wyy
-                if mode == 0:
-                    # only w / wyy are non-negative; wy may be negative
-                    H[:, ds, :, 1] = H_prev[:, ps, :, 1] - Hb[:, :, :, 1]
-                del Hb
-            nleft_pre = None
-            ok_h = None
-            naw_h = None
-            if can_split:
-                sel = self._col_sel(n_front, depth) if direct else None
-                cm = None if (direct and self.dev.type == "cuda") else self._col_mask(n_front, depth, sel=sel,
-                                                                                      allow=f_allow)
+    def _start_level(self, fr, depth):
+        """Per-level state of the split search: parent records (_adapt_range), monotone bounds."""
+        self._level = self._depth = depth
+        nxt = self._adapt_next
+        self._adapt_par = None if (depth == 0 or nxt is None) else nxt + (int(fr.id.size),)
+        self._rng_par = None if depth == 0 else self._rng_cur
+        self._rng_cur = self._adapt_next = None
+        if fr.lo is not None and bool(np.isfinite(fr.lo).any() | np.isfinite(fr.hi).any()):
+            self._bnd = torch.as_tensor(np.stack([fr.lo, fr.hi], 1), dtype=torch.float64, device=self.dev)
+        else:
+            self._bnd = None
+        self._bnd_off = 0
+
+    def _swap_rows(self):
+        """The partition's output becomes the current row order (and payload)."""
+        self.ridx, self.ridx2 = self.ridx2, self.ridx
+        if self._pos1 is not None:
+            self._pos1.reverse()
+
+    def _part_payload(self):
+        return (self._pos1[0], None, self._pos1[1], None) if self._pos1 is not None else None
+
+    def _level_hist(self, fr, va, vb, mode, depth, la, H_prev, wyy_prev, wyy_level):
+        """(H, node w*y*y sums) of a level: the look-ahead's result, a build from the rows,
+        or each pair's lighter child built and its sibling derived as parent minus built."""
+        n_front = int(fr.id.size)
+        if la is not None:
+            # built on the device before the host read the previous level's decisions (_maybe_lookahead)
+            if tree_ops.env("H2O3_LA_CHECK") == "1":
+                self._la_check(la, fr.p_build, fr.p_der, fr.p_par)
+            return la[0][:, :n_front].contiguous(), (la[1][:n_front] if la[1] is not None else None)
+        if depth == 0 or H_prev is None:
+            H = self._build_hist(self.ridx, va, vb, mode, fr.st, fr.ct)
+            return H, self._last_wyy
+        Hb = self._build_hist(self.ridx, va, vb, mode, fr.st[fr.p_build], fr.ct[fr.p_build])
+        wyy_b = self._last_wyy if mode == 0 else None
+        if self.dev.type == "cuda":
+            # copy + parent-minus-built subtraction in one kernel
+            H, wyy_n = tree_ops.hist_sibling(Hb, H_prev, fr.p_build, fr.p_der, fr.p_par, n_front, _clamp_mask(mode),
+                                             wyy_b=wyy_b, wyy_prev=wyy_prev if wyy_b is not None else None)
+            return H, (wyy_n if wyy_n is not None else wyy_level)
+        H = torch.empty((Hb.shape[0], n_front) + tuple(Hb.shape[2:]), dtype=Hb.dtype, device=Hb.device)
+        bs = torch.as_tensor(fr.p_build, device=Hb.device)
+        ds = torch.as_tensor(fr.p_der, device=Hb.device)
+        ps = torch.as_tensor(fr.p_par, device=Hb.device)
+        H[:, bs] = Hb
+        H[:, ds] = (H_prev[:, ps] - Hb).clamp_min_(0) if mode != 1 else (H_prev[:, ps] - Hb)
+        if wyy_b is not None:
+            wyy_level = torch.empty(n_front, dtype=torch.float64, device=Hb.device)
+            wyy_level[bs] = wyy_b
+            wyy_level[ds] = wyy_prev[ps] - wyy_b
+        if mode == 0:
+            # only w / wyy are non-negative; wy may be negative
+            H[:, ds, :, 1] = H_prev[:, ps, :, 1] - Hb[:, :, :, 1]
+        return H, wyy_level
+
+    def _level_splits(self, fr, va, vb, mode, depth, H, wyy_level, direct, chunked, want_pk):
+        """Best split per frontier node (a split search's dict): from the level histogram,
+        from row-direct pair histograms, or chunk by chunk under the histogram budget."""
+        p, bd = self.p, self.bd
+        n_front = int(fr.id.size)
+        on_dev = self.dev.type == "cuda"
+        sel = self._col_sel(n_front, depth) if direct else None
+        cm = None if (direct and on_dev) else self._col_mask(n_front, depth, sel=sel, allow=fr.allow)
+        with phase("tree.split"):
+            if direct and on_dev:
+                return self._pair_direct_dev(self.ridx, va, vb, mode, fr.st, fr.ct, sel)
+            if direct:
+                return self._pair_direct_splits(self.ridx, va, vb, mode, fr.st, fr.ct, cm)
+            if not chunked:
                 # node totals of w*y*y (only the total enters the SE split test),
                 # fused into the histogram kernel; derived siblings by subtraction
-                node_wyy = wyy_level if mode == 0 else None
-                with phase("tree.split"):
-                    if direct and self.dev.type == "cuda":
-                        sp = self._pair_direct_dev(ridx, va, vb, mode, f_st, f_ct, sel)
-                    elif direct:
-                        sp = self._pair_direct_splits(ridx, va, vb, mode, f_st, f_ct, cm)
-                    elif chunked:
-                        per = max(1, int(p.hist_mem_budget // max(1, self.Fpad * bd.Bs * C_ * 8)))
-                        parts = []
-                        need = self._hist_need(cm)
-                        for a in range(0, n_front, per):
-                            Hc = self._build_hist(ridx, va, vb, mode, f_st[a:a + per], f_ct[a:a + per],
-                                                  need_mask=None if need is None else need[a:a + per])
-                            wyy_c = self._last_wyy if mode == 0 else None
-                            self._bnd_off = a
-                            parts.append(self._find_splits(Hc, cm[a:a + per], wyy_c, want_pk=False))
-                            del Hc
-                        self._bnd_off = 0
-                        sp = {k: (torch.cat([q[k] for q in parts], 0) if parts[0].get(k) is not None else None)
-                              for k in parts[0]}
-                    else:
-                        sp = self._find_splits(H, cm, node_wyy, want_pk=async_part)
-                nn_ = n_front
-                if async_part and "pk" in sp:
-                    pkd = sp["pk"]
-                    with phase("tree.partition"):
-                        # no ridx2 <- ridx copy: every frontier segment is rewritten (non-splitting
-                        # nodes in place), earlier leaves are identical in both buffers already
-                        pay = (self._pos1[0], None, self._pos1[1], None) if self._pos1 is not None else None
-                        tree_ops.partition_async(bd, ridx, ridx2, sp["feat_i32"], sp["mask"], f_st, f_ct,
-                                                 payload=pay, pk=pkd, pk_col=11)
-                    # the record's copy is queued BEFORE the look-ahead kernels, so
-                    # the host gets it while the GPU builds the next level
-                    pk_h = self._d2h_async(pkd)
-                    self._maybe_lookahead(pkd, (10, 11, 4 + (mode == 1), 6 + (mode == 1)), f_st, f_ct, mode, va,
-                                          vb, ridx2, H, wyy_level, depth, level_bytes, chunked)
-                    pk = self._d2h_wait(pk_h)
-                    self._flush_masks(tb)
-                    ok_h = pk[:, 10] > 0
-                    nleft_pre = pk[:, 11].astype(np.int64)
-                    naw_h = pk[:, 12] if pk.shape[1] > 12 else None
-                cols = [] if nleft_pre is not None else [
-                    sp["gain"].view(nn_, 1).to(torch.float64), sp["feat"].view(nn_, 1).to(torch.float64),
-                    sp["t"].view(nn_, 1).to(torch.float64), sp["opt"].view(nn_, 1).to(torch.float64),
-                    sp["L"].to(torch.float64), sp["R"].to(torch.float64), sp["tot"].to(torch.float64)]
-                naw_d = sp["naw"].to(torch.float64) if (cols and sp.get("naw") is not None) else None
-                if naw_d is None and cols and H is not None and self.W == 1 and mode == 0 and H.shape[1] == nn_:
-                    # the winner's NA-bin weight per node (per-node NA direction rule below)
-                    fi = sp["feat"].to(torch.int64).clamp(0, H.shape[0] - 1)
-                    naw_d = H[fi, torch.arange(nn_, device=H.device), H.shape[2] - 1, 0].to(torch.float64)
-                if async_part and nleft_pre is None:
-                    # split decision + partition of the whole frontier on the device: no
-                    # host round trip between the split search and the row partition
-                    tot_d = sp["tot"].to(torch.float64)
-                    w_d = (tot_d[:, 0] if mode != 1 else tot_d[:, 1]) + (tot_d[:, 2] if mode == 3 else 0.0)
-                    ok_d = torch.isfinite(sp["gain"].to(torch.float64))
-                    if p.criterion != "xgb":
-                        ok_d &= w_d >= 2 * p.min_rows
-                    feat_all = torch.where(ok_d, sp["feat"].to(torch.int64),
-                                           torch.zeros_like(sp["feat"].to(torch.int64)))
-                    mask_all = torch.where(ok_d.view(-1, 1), sp["mask"].to(torch.uint8),
-                                           torch.ones_like(sp["mask"], dtype=torch.uint8))
-                    with phase("tree.partition"):
-                        pay = (self._pos1[0], None, self._pos1[1], None) if self._pos1 is not None else None
-                        nleft_d = tree_ops.partition_async(bd, ridx, ridx2, feat_all, mask_all, f_st, f_ct,
-                                                           payload=pay)
-                    cols += [ok_d.view(nn_, 1).to(torch.float64), nleft_d.view(nn_, 1).to(torch.float64)]
-                # ONE device->host transfer of every per-node scalar of the level
-                if cols:
-                    if naw_d is not None:
-                        cols.append(naw_d.view(nn_, 1))      # last column
-                    rec = torch.cat(cols, 1)
-                    pk_h = self._d2h_async(rec)
-                    if async_part:
-                        self._maybe_lookahead(rec, (4 + 3 * C, 5 + 3 * C, 4 + (mode == 1), 4 + C + (mode == 1)),
-                                              f_st, f_ct, mode, va, vb, ridx2, H, wyy_level, depth, level_bytes,
-                                              chunked)
-                    pk = self._d2h_wait(pk_h)
-                    self._flush_masks(tb)
-                    if async_part:
-                        ok_h = pk[:, 4 + 3 * C] > 0
-                        nleft_pre = pk[:, 5 + 3 * C].astype(np.int64)
-                    naw_h = pk[:, -1] if naw_d is not None else None
-                gains = pk[:, 0]
-                feats = pk[:, 1].astype(np.int64)
-                t_a = pk[:, 2].astype(np.int64)
-                opt_a = pk[:, 3].astype(np.int64)
-                Ls = pk[:, 4:4 + C]
-                Rs = pk[:, 4 + C:4 + 2 * C]
-                tots = pk[:, 4 + 2 * C:4 + 3 * C]
-            else:
-                # totals only
-                tots = self._totals(H).numpy() if H is not None else f_tot
-                gains = None
-            tots = np.asarray(tots, dtype=np.float64)
-            w_a = (tots[:, 0] if mode != 1 else tots[:, 1]) + (tots[:, 2] if mode == 3 else 0.0)
-            tb.weight[f_id] = w_a
-            if ok_h is not None:
-                ok = np.asarray(ok_h, dtype=bool).copy()
-            elif can_split and gains is not None:
-                ok = np.isfinite(gains)
-                if p.criterion != "xgb":
-                    ok &= w_a >= 2 * p.min_rows
-            else:
-                ok = np.zeros(n_front, dtype=bool)
-            if p.max_leaves:
-                # leaf budget, node by node in frontier order (the leaves of this
-                # level counted as they are decided); lossguide spends it on the
-                # largest loss reductions first (XGBoost's best-first expansion
-                # order among the nodes of a level)
-                n_leaves = sum(part[0].size for part in leaf_parts)
-                n_split = 0
-                order = range(n_front)
-                if p.leaf_budget_by_gain and gains is not None:
-                    order = np.argsort(-np.where(ok, gains, -np.inf), kind="stable")
-                for i in order:
-                    if ok[i] and (n_leaves + n_front + n_split + 1) > p.max_leaves:
-                        ok[i] = False
-                    if ok[i]:
-                        n_split += 1
-                    else:
-                        n_leaves += 1
-            lf = ~ok
-            if lf.any():
-                leaf_parts.append((f_id[lf], f_st[lf], f_ct[lf], tots[lf]))
-            sids = np.nonzero(ok)[0]
-            if sids.size == 0:
-                if nleft_pre is not None:
-                    ridx, ridx2 = ridx2, ridx   # the (identity) partition already ran
-                    if self._pos1 is not None:
-                        self._pos1.reverse()
-                break
-            # record the splits in the tree (vectorized over the level)
-            k = int(sids.size)
-            nid_s = f_id[sids]
-            f_s = feats[sids]
-            opt_s = opt_a[sids]
-            t_s = t_a[sids]
-            Lsel, Rsel = Ls[sids], Rs[sids]
-            wl_a = (Lsel[:, 0] if mode != 1 else Lsel[:, 1]) + (Lsel[:, 2] if mode == 3 else 0.0)
-            wr_a = (Rsel[:, 0] if mode != 1 else Rsel[:, 1]) + (Rsel[:, 2] if mode == 3 else 0.0)
-            build_left = wl_a <= wr_a
-            first = tb.add_children(depth + 1, Lsel[:, 0], Rsel[:, 0])
-            lid = first + 2 * np.arange(k, dtype=np.int64)
-            tb.feat[nid_s] = f_s
-            tb.gain[nid_s] = gains[sids]
-            na_s = opt_s == 1
-            hn = getattr(self.bd, "has_na", None)
-            if p.criterion != "xgb" and (naw_h is not None or (hn is not None and len(hn) == self.bd.F)):
-                # no NA weight reached THIS node on the split column: NAs of later
-                # data go to the heavier child (DTree.java:1475-1478 decides per
-                # node, nasplit == None); without the node's NA weight (chunked /
-                # pair / multi-rank torch paths) the training-wide flag stands in
-                no_na = (np.asarray(naw_h)[sids] == 0) if naw_h is not None else ~np.asarray(hn, dtype=bool)[f_s]
-                free = no_na & (opt_s != 2) & ~is_cat_np[f_s]
-                na_s = np.where(free, wl_a > wr_a, na_s)
-            tb.na_left[nid_s] = na_s
-            if self._adaptive:
-                self._adapt_next = (sids.copy(), np.asarray(f_s).copy(), np.asarray(t_s).copy(),
-                                    np.asarray(opt_s).copy())
-            tb.left[nid_s] = lid
-            tb.right[nid_s] = lid + 1
-            cat_s = is_cat_np[f_s]
-            num = ~cat_s
-            if num.any():
-                tb.thr[nid_s[num]] = np.where(opt_s[num] == 2, np.inf, cutmat[f_s[num], np.minimum(t_s[num],
-                                                                                                   cutmat.shape[1] - 1)])
-                tb.split_code[nid_s[num]] = t_s[num]
-            all_split = k == n_front
-            masks = None
-            if cat_s.any() or nleft_pre is None:
-                masks = sp["mask"] if all_split else sp["mask"][tree_ops._h2d(sids, sp["mask"].device)]
-            if cat_s.any():
-                # only the categorical splits' mask rows cross to the host (one gather + copy)
-                cj = np.nonzero(cat_s)[0]
-                mk = masks[tree_ops._h2d(cj, masks.device)] if cj.size < k else masks
-                masks_h = None
-                if mk.is_cuda and tree_ops.env("H2O3_ASYNC_MASKS", "1") == "1":
-                    # asynchronous copy into a pinned staging buffer: the rows are
-                    # collected after the next level's record arrives (the GPU has
-                    # long finished the copy by then) instead of a blocking .cpu()
-                    self._flush_masks(tb)
-                    need = mk.numel()
-                    st_buf = self.__dict__.get("_mask_stage")
-                    if st_buf is None or st_buf.numel() < need:
-                        st_buf = self._mask_stage = torch.empty(max(need, 1 << 20), dtype=torch.uint8,
-                                                                pin_memory=True)
-                    st_buf[:need].view(mk.shape).copy_(mk, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                else:
-                    masks_h = mk.cpu().numpy()
-                tb.is_cat[nid_s[cj]] = True
-                tb.thr[nid_s[cj]] = np.nan
-                fcj = f_s[cj]
-                for f in np.unique(fcj).tolist():
-                    if f not in tb.cat_lvm:
-                        # level -> code of the mask row (grouped high-cardinality levels share a code)
-                        card = bd.cat_card[f]
-                        tb.cat_lvm[f] = np.arange(card) if (bd.cat_group[f] == 1 and card <= bd.Bs - 1) else \
-                            np.minimum(np.arange(card) // bd.cat_group[f], bd.Bs - 2)
-                if masks_h is not None:
-                    tb.cat_parts.append((nid_s[cj].astype(np.int64), fcj.astype(np.int64), masks_h))
-                else:
-                    self._mask_pend = (nid_s[cj].astype(np.int64), fcj.astype(np.int64), tuple(mk.shape), ev)
-            st_s, ct_s = f_st[sids], f_ct[sids]
-            # partition
-            if nleft_pre is not None:
-                nleft = nleft_pre[sids]
-                if self._pos1 is not None:
-                    self._pos1.reverse()
-            else:
-                with phase("tree.partition"):
-                    ridx2.copy_(ridx)
-                    if self.use_payload:
-                        pa2.copy_(pa)
-                        pb2.copy_(pb)
-                    pay = (pa, pb, pa2, pb2) if self.use_payload else None
-                    if self._pos1 is not None:
-                        pay = (self._pos1[0], None, self._pos1[1], None)
-                    nleft = np.asarray(tree_ops.partition(bd, ridx, ridx2, f_s, masks, st_s, ct_s, payload=pay),
-                                       dtype=np.int64)
-                    if self._pos1 is not None:
-                        self._pos1.reverse()
-            ridx, ridx2 = ridx2, ridx
-            if self.use_payload:
-                pa, pa2, pb, pb2 = pa2, pa, pb2, pb
-                va, vb = pa, pb
-            # next frontier: (left, right) of every split node, in order
-            f_id = np.stack([lid, lid + 1], 1).reshape(-1)
-            f_st = np.stack([st_s, st_s + nleft], 1).reshape(-1)
-            f_ct = np.stack([nleft, ct_s - nleft], 1).reshape(-1)
-            f_tot = np.stack([Lsel, Rsel], 1).reshape(2 * k, -1)
-            if f_allow is not None:
-                # nextLevelInteractionConstraints: branch set ∩ the split feature's set
-                ca = f_allow[tree_ops._h2d(sids, self.dev)] & ics_t[tree_ops._h2d(f_s, self.dev)]
-                f_allow = torch.repeat_interleave(ca, 2, dim=0)
-            if mono_b:
-                f_lo, f_hi = self._child_bounds(f_lo[sids], f_hi[sids], f_s, cat_s, np.asarray(Lsel, dtype=np.float64),
-                                                np.asarray(Rsel, dtype=np.float64), mode)
-            jj = 2 * np.arange(k, dtype=np.int64)
-            p_build = jj + (~build_left)
-            p_der = jj + build_left
-            # parent hists for the next level (only split nodes)
-            if H is None:
-                H_prev, wyy_prev = None, None   # chunked level: next level builds from rows
-                p_par = np.arange(k, dtype=np.int64)
-            elif self.dev.type == "cuda":
-                # the sibling kernel indexes the parent level directly: keep the
-                # whole level and point the pairs at their parents' slots
-                H_prev = H
-                wyy_prev = wyy_level if mode == 0 else None
-                p_par = sids.astype(np.int64)
-            else:
-                sid = torch.as_tensor(sids, device=H.device)
-                H_prev = H[:, sid]
-                wyy_prev = wyy_level[sid] if (mode == 0 and wyy_level is not None) else None
-                p_par = np.arange(k, dtype=np.int64)
-            depth += 1
-            level += 1
-        del coll._TAG[ntag - 1:]
-        self._flush_masks(tb)
-        tree = tb.to_tree()
-        if leaf_parts:
-            leaf_ids = np.concatenate([q[0] for q in leaf_parts])
-            leaf_st = np.concatenate([q[1] for q in leaf_parts])
-            leaf_ct = np.concatenate([q[2] for q in leaf_parts])
-            leaf_tot_np = np.concatenate([q[3] for q in leaf_parts], 0)
+                return self._find_splits(H, cm, wyy_level if mode == 0 else None, want_pk=want_pk)
+            per = max(1, int(p.hist_mem_budget // max(1, self.Fpad * bd.Bs * tree_ops.channels(mode) * 8)))
+            parts = []
+            need = self._hist_need(cm)
+            for a in range(0, n_front, per):
+                Hc = self._build_hist(self.ridx, va, vb, mode, fr.st[a:a + per], fr.ct[a:a + per],
+                                      need_mask=None if need is None else need[a:a + per])
+                wyy_c = self._last_wyy if mode == 0 else None
+                self._bnd_off = a
+                parts.append(self._find_splits(Hc, cm[a:a + per], wyy_c, want_pk=False))
+                del Hc
+            self._bnd_off = 0
+            return {k: (torch.cat([q[k] for q in parts], 0) if parts[0].get(k) is not None else None)
+                    for k in parts[0]}
+
+    def _assemble_record(self, sp, H, mode, part):
+        """(record, feat, mask) of a split search that returned loose tensors: the level
+        record (record.py) put together on the device.  With part, OK holds the split
+        decision and (feat, mask) partition the whole frontier (an all-ones mask keeps a
+        non-splitting node in place), which writes NL; without, OK / NL are filler."""
+        p = self.p
+        n = sp["gain"].shape[0]
+        f64 = torch.float64
+        gain, tot = sp["gain"].view(n, 1).to(f64), sp["tot"].to(f64)
+        cols = [gain, sp["feat"].view(n, 1).to(f64), sp["t"].view(n, 1).to(f64), sp["opt"].view(n, 1).to(f64),
+                sp["L"].to(f64), sp["R"].to(f64), tot]
+        naw = sp["naw"].to(f64) if sp.get("naw") is not None else None
+        if naw is None and H is not None and self.W == 1 and mode == 0 and H.shape[1] == n:
+            # the winner's NA-bin weight per node (per-node NA direction rule of _write_splits)
+            fi = sp["feat"].to(torch.int64).clamp(0, H.shape[0] - 1)
+            naw = H[fi, torch.arange(n, device=H.device), H.shape[2] - 1, 0].to(f64)
+        feat, mask = sp["feat"], sp["mask"]
+        if part:
+            ok = torch.isfinite(gain.view(n))
+            if p.criterion != "xgb":
+                ok &= _row_weight(tot, mode) >= 2 * p.min_rows
+            feat = feat.to(torch.int64)
+            feat = torch.where(ok, feat, torch.zeros_like(feat))
+            mask = torch.where(ok.view(-1, 1), mask.to(torch.uint8), torch.ones_like(mask, dtype=torch.uint8))
+            filler = ok.view(n, 1).to(f64)
         else:
-            leaf_ids = leaf_st = leaf_ct = np.zeros(0, dtype=np.int64)
-            leaf_tot_np = np.zeros((0, C))
-        leaves = leaf_ids.tolist()
-        lids = list(range(len(leaves)))
-        nid = None
-        if want_nid:
-            with phase("tree.nid"):
-                nid = tree_ops.fill_nid(ridx, np.arange(len(leaves), dtype=np.int64), leaf_st, leaf_ct, N)
-        self.ridx, self.ridx2 = ridx, ridx2
-        self._pay = [pa, pb, pa2, pb2]
-        self.last_segs = (lids, leaf_st.tolist(), leaf_ct.tolist())
-        leaf_tot_t = torch.from_numpy(np.ascontiguousarray(leaf_tot_np, dtype=np.float64))
-        return tree, nid, leaves, leaf_tot_t
+            filler = gain
+        cols += [filler, filler]
+        if naw is not None:
+            cols.append(naw.view(n, 1))
+        return torch.cat(cols, 1), feat, mask
+
+    def _level_record(self, sp, fr, tb, va, vb, mode, depth, H, wyy_level, level_bytes, chunked, part):
+        """The one consumer of the level record, whichever split search made it: partition
+        of the whole frontier on the device (no host round trip after the split search),
+        the level's single device->host transfer, the look-ahead, then the decoded record."""
+        C = tree_ops.channels(mode)
+        c = rec_cols(C)
+        if "pk" in sp:
+            rec, feat, mask = sp["pk"], sp["feat_i32"], sp["mask"]
+        else:
+            rec, feat, mask = self._assemble_record(sp, H, mode, part)
+        if part:
+            with phase("tree.partition"):
+                # no ridx2 <- ridx copy: every frontier segment is rewritten (non-splitting
+                # nodes in place), earlier leaves are identical in both buffers already
+                tree_ops.partition_async(self.bd, self.ridx, self.ridx2, feat, mask, fr.st, fr.ct,
+                                         payload=self._part_payload(), pk=rec, pk_col=c.NL)
+        # the record's copy is queued BEFORE the look-ahead kernels, so the
+        # host gets it while the GPU builds the next level
+        rec_h = self._d2h_async(rec)
+        if part:
+            w = weight_col(mode)
+            self._maybe_lookahead(rec, (c.OK, c.NL, c.L + w, c.R + w), fr.st, fr.ct, mode, va, vb, self.ridx2, H,
+                                  wyy_level, depth, level_bytes, chunked)
+        rec_np = self._d2h_wait(rec_h)
+        self._flush_masks(tb)
+        return decode(rec_np, C, part)
+
+    def _leaf_budget(self, ok, gains, n_leaves):
+        """max_leaves: clear ok (in place) where a split would exceed the leaf budget, node by
+        node in frontier order (this level's leaves counted as they are decided; n_leaves: those
+        of earlier levels); lossguide spends it on the largest loss reductions first (XGBoost's
+        best-first expansion order among the nodes of a level)."""
+        p = self.p
+        n_front = ok.size
+        n_split = 0
+        order = range(n_front)
+        if p.leaf_budget_by_gain and gains is not None:
+            order = np.argsort(-np.where(ok, gains, -np.inf), kind="stable")
+        for i in order:
+            if ok[i] and (n_leaves + n_front + n_split + 1) > p.max_leaves:
+                ok[i] = False
+            if ok[i]:
+                n_split += 1
+            else:
+                n_leaves += 1
+
+    def _write_splits(self, tb, nid_s, depth, dec, sids, f_s, cat_s, Lsel, Rsel, wl_a, wr_a):
+        """Record the level's splits in the tree (vectorized); returns the left child ids."""
+        p = self.p
+        opt_s, t_s = dec.opt[sids], dec.t[sids]
+        first = tb.add_children(depth + 1, Lsel[:, 0], Rsel[:, 0])
+        lid = first + 2 * np.arange(sids.size, dtype=np.int64)
+        tb.feat[nid_s] = f_s
+        tb.gain[nid_s] = dec.gain[sids]
+        na_s = opt_s == 1
+        hn = getattr(self.bd, "has_na", None)
+        if p.criterion != "xgb" and (dec.naw is not None or (hn is not None and len(hn) == self.bd.F)):
+            # no NA weight reached THIS node on the split column: NAs of later
+            # data go to the heavier child (DTree.java:1475-1478 decides per
+            # node, nasplit == None); without the node's NA weight (chunked /
+            # pair / multi-rank torch paths) the training-wide flag stands in
+            no_na = (dec.naw[sids] == 0) if dec.naw is not None else ~np.asarray(hn, dtype=bool)[f_s]
+            free = no_na & (opt_s != 2) & ~cat_s
+            na_s = np.where(free, wl_a > wr_a, na_s)
+        tb.na_left[nid_s] = na_s
+        if self._adaptive:
+            self._adapt_next = (sids.copy(), f_s.copy(), t_s.copy(), opt_s.copy())
+        tb.left[nid_s] = lid
+        tb.right[nid_s] = lid + 1
+        num = ~cat_s
+        if num.any():
+            cutmat = self._cut_matrix()
+            tb.thr[nid_s[num]] = np.where(opt_s[num] == 2, np.inf,
+                                          cutmat[f_s[num], np.minimum(t_s[num], cutmat.shape[1] - 1)])
+            tb.split_code[nid_s[num]] = t_s[num]
+        return lid
+
+    def _stage_cat_masks(self, tb, masks, nid_s, f_s, cat_s):
+        """The categorical splits' go-left masks: only those rows cross to the host."""
+        bd = self.bd
+        cj = np.nonzero(cat_s)[0]
+        mk = masks[tree_ops._h2d(cj, masks.device)] if cj.size < cat_s.size else masks
+        nodes, fcj = nid_s[cj].astype(np.int64), f_s[cj].astype(np.int64)
+        tb.is_cat[nodes] = True
+        tb.thr[nodes] = np.nan
+        for f in np.unique(fcj).tolist():
+            if f not in tb.cat_lvm:
+                # level -> code of the mask row (grouped high-cardinality levels share a code)
+                card = bd.cat_card[f]
+                tb.cat_lvm[f] = np.arange(card) if (bd.cat_group[f] == 1 and card <= bd.Bs - 1) else \
+                    np.minimum(np.arange(card) // bd.cat_group[f], bd.Bs - 2)
+        if not (mk.is_cuda and tree_ops.env("H2O3_ASYNC_MASKS", "1") == "1"):
+            tb.cat_parts.append((nodes, fcj, mk.cpu().numpy()))
+            return
+        # asynchronous copy into a pinned staging buffer: the rows are
+        # collected after the next level's record arrives (the GPU has
+        # long finished the copy by then) instead of a blocking .cpu()
+        self._flush_masks(tb)
+        need = mk.numel()
+        if self._mask_stage is None or self._mask_stage.numel() < need:
+            self._mask_stage = torch.empty(max(need, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        self._mask_stage[:need].view(mk.shape).copy_(mk, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._mask_pend = (nodes, fcj, tuple(mk.shape), ev)
+
+    def _partition_sync(self, f_s, masks, st_s, ct_s):
+        """Partition the splitting nodes' rows after the host decided; returns the left counts."""
+        with phase("tree.partition"):
+            self.ridx2.copy_(self.ridx)
+            return np.asarray(tree_ops.partition(self.bd, self.ridx, self.ridx2, f_s, masks, st_s, ct_s,
+                                                 payload=self._part_payload()), dtype=np.int64)
+
+    def _next_frontier(self, fr, sids, lid, nleft, f_s, cat_s, Lsel, Rsel, build_left, ics_t, mode, H, wyy_level):
+        """(frontier, parent histograms, parent w*y*y) of the next level: (left, right) of every
+        split node, in order; the lighter child is built from rows, its sibling derived."""
+        k = int(sids.size)
+        st_s, ct_s = fr.st[sids], fr.ct[sids]
+        jj = 2 * np.arange(k, dtype=np.int64)
+        nx = _Frontier(id=np.stack([lid, lid + 1], 1).reshape(-1),
+                       st=np.stack([st_s, st_s + nleft], 1).reshape(-1),
+                       ct=np.stack([nleft, ct_s - nleft], 1).reshape(-1),
+                       tot=np.stack([Lsel, Rsel], 1).reshape(2 * k, -1),
+                       p_build=jj + (~build_left), p_der=jj + build_left)
+        if fr.allow is not None:
+            # nextLevelInteractionConstraints: branch set ∩ the split feature's set
+            ca = fr.allow[tree_ops._h2d(sids, self.dev)] & ics_t[tree_ops._h2d(f_s, self.dev)]
+            nx.allow = torch.repeat_interleave(ca, 2, dim=0)
+        if fr.lo is not None:
+            nx.lo, nx.hi = self._child_bounds(fr.lo[sids], fr.hi[sids], f_s, cat_s, np.asarray(Lsel, dtype=np.float64),
+                                              np.asarray(Rsel, dtype=np.float64), mode)
+        # parent hists for the next level (only split nodes)
+        if H is None:
+            nx.p_par = np.arange(k, dtype=np.int64)
+            return nx, None, None   # chunked level: next level builds from rows
+        if self.dev.type == "cuda":
+            # the sibling kernel indexes the parent level directly: keep the
+            # whole level and point the pairs at their parents' slots
+            nx.p_par = sids.astype(np.int64)
+            return nx, H, (wyy_level if mode == 0 else None)
+        sid = torch.as_tensor(sids, device=H.device)
+        nx.p_par = np.arange(k, dtype=np.int64)
+        return nx, H[:, sid], (wyy_level[sid] if (mode == 0 and wyy_level is not None) else None)
 
     def _d2h_async(self, t):
         """Queue a device->host copy of t into a reusable pinned slot; returns
         (host view, event).  CPU tensors pass through."""
         if t.device.type != "cuda":
             return (t, None, 0)
-        ring = self.__dict__.setdefault("_d2h_ring", [None, None])
-        k = self.__dict__.get("_d2h_k", 0)
+        ring, k = self._d2h_ring, self._d2h_k
         self._d2h_k = k ^ 1
         buf = ring[k]
         if buf is None or buf.numel() < t.numel():
@@ -2035,10 +2025,10 @@ class TreeGrower:
         h = buf[:t.numel()].view(t.shape)
         h.copy_(t, non_blocking=True)
         # one reusable event per slot, recorded on the stream cached by grow()
-        evs = self.__dict__.setdefault("_d2h_ev", [None, None])
+        evs = self._d2h_ev
         if evs[k] is None:
             evs[k] = torch.cuda.Event()
-        st = getattr(self, "_stream_obj", None)
+        st = self._stream_obj
         evs[k].record(st if st is not None else torch.cuda.current_stream())
         # uploads staged after this record (the look-ahead) are NOT covered
         return (h, evs[k], tree_ops.upload_mark())
@@ -2066,22 +2056,17 @@ class TreeGrower:
             return
         if 2 * level_bytes + H.numel() * 8 > p.hist_mem_budget:
             return
-        posv = False
-        va_n, vb_n = va, vb
-        if mode == 0 and getattr(self, "_pos1", None) is not None:
-            va_n, vb_n, posv = self._pos1[1], None, True     # the payload the partition just moved
-        elif mode == 0 and getattr(self, "_va_eff", None) is not None:
-            va_n, vb_n = self._va_eff, None
+        va_n, vb_n, posv = self._hist_response(va, vb, mode, moved=True)   # the payload the partition just moved
         with phase("tree.hist"), phase("tree.hist.lookahead"):
             r = tree_ops.hist_build_dev(self.bd, ridx_next, va_n, vb_n, mode, rec, cols, f_st, f_ct, self._vmax,
-                                        posv=posv, unit_w=getattr(self, "_unit_w", False))
+                                        posv=posv, unit_w=self._unit_w)
             if r is None:
                 return
             Hb, wyy_b, slots, cnts = r
             if self.W > 1:
                 Hb, wyy_b = self._rs_hist_wyy(Hb, wyy_b)
-            clamp = {0: 0b1, 1: 0b0}.get(mode, (1 << tree_ops.channels(mode)) - 1)
-            Hn, wyy_n = tree_ops.hist_sibling_dev(Hb, H, slots, cnts, clamp, wyy_b=wyy_b if mode == 0 else None,
+            Hn, wyy_n = tree_ops.hist_sibling_dev(Hb, H, slots, cnts, _clamp_mask(mode),
+                                                  wyy_b=wyy_b if mode == 0 else None,
                                                   wyy_prev=wyy_level if mode == 0 else None)
         self._la = (Hn, wyy_n, slots, cnts)
 
@@ -2097,7 +2082,7 @@ class TreeGrower:
     def _cut_matrix(self):
         """[F, max_cuts + 1] numeric split values by (feature, threshold code):
         cuts[f][t], +inf past the last cut (BinnedData.split_value)."""
-        cm = getattr(self, "_cutmat", None)
+        cm = self._cutmat
         if cm is None:
             bd = self.bd
             w = 1 + max([len(c) for c in bd.cuts if c is not None] or [0])

@@ -317,7 +317,7 @@ class GBMDriver:
                     tree, nid, leaves, tot = self.grower.grow(z.contiguous(), w.contiguous(), 0,
                                                               want_nid=not (fused or posleaf), vmax=vmax_h,
                                                               unit_w=self._base_unit)
-            zpos = self.grower._pos1[0] if (posleaf and getattr(self.grower, "_pos1", None) is not None) else None
+            zpos = self.grower.pos_payload() if posleaf else None
             if posleaf and zpos is None:
                 posleaf = False
                 nid = tree_ops.fill_nid(self.grower.ridx, *self.grower.last_segs, z.shape[0])
@@ -472,7 +472,7 @@ class GBMDriver:
         for k in range(K):
             z = (self.Y[:, k] - P[:, k]).contiguous()
             tree, nid, leaves, tot = self.grower.grow(z, wc, 0, want_nid=False, vmax=[1.0, 1.0], unit_w=True)
-            zpos = self.grower._pos1[0] if getattr(self.grower, "_pos1", None) is not None else None
+            zpos = self.grower.pos_payload()
             lids, st, ct = self.grower.last_segs
             L = len(leaves)
             if zpos is not None:
