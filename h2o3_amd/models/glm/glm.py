@@ -23,6 +23,8 @@ from __future__ import annotations
 import math
 import os
 import time
+from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -165,13 +167,99 @@ def _soft(x, t):
 _CD = []
 
 
-def _narrow_max():
-    """Widest padded design on the narrow fused IRLS kernel (32-wide tile
-    pairs, one pass); wider designs take the wide path (eta pass + 256-tile
-    bf16 MFMA Gram).  128: at 10M x 200 (AutoML's GLM step without CV) the
-    wide path trains in 2.1 s against 11.4 s on the 32-wide tile pairs, with
-    the same tiers and fp64-level coefficients (profiles/glm_f64_r6/)."""
-    return int(os.environ.get("H2O3_GLM_NARROW_MAX", "128"))
+@dataclass(frozen=True)
+class GlmSwitches:
+    """The A/B switches of the GLM IRLS path, one field per H2O3_* variable
+    (named beside it).  A GLMDriver reads them once, at construction."""
+    # widest padded design on the narrow fused IRLS kernel (32-wide tile pairs,
+    # one pass); wider designs take the wide path (eta pass + 256-tile bf16 MFMA
+    # Gram).  128: at 10M x 200 (AutoML's GLM step without CV) the wide path
+    # trains in 2.1 s against 11.4 s on the 32-wide tile pairs, with the same
+    # tiers and fp64-level coefficients (profiles/glm_f64_r6/)
+    narrow_max: int = 128        # H2O3_GLM_NARROW_MAX
+    bf16: bool = True            # H2O3_GLM_BF16: plain-bf16 Hessian tier of the narrow kernel
+    bf3: bool = True             # H2O3_GLM_BF3: bf16x3 MFMA on the Pp = 128 kernel (off: f32 MFMA)
+    wide_bf16: bool = True       # H2O3_GLM_WIDE_BF16: plain-bf16 tier of the fused wide Gram
+    dev_solve: bool = True       # H2O3_GLM_DEV_SOLVE: wide systems conditioned / solved on the device
+    exact_grad: bool = True      # H2O3_GLM_EXACT_GRAD: off, the right-hand side is the Gram's X'Wz column
+    f64_mfma: bool = True        # H2O3_GLM_F64_MFMA: fp64 tier on the f64 matrix-core kernels
+    tiers: bool = True           # H2O3_GLM_TIERS: Hessian precision tiers from the condition number
+    wide_fused: bool = True      # H2O3_GLM_WIDE_FUSED: off, the split + library GEMM wide pass
+    wide_gram: str = "bf3"       # H2O3_WIDE_GRAM: anything else, the f32 library GEMM wide Gram
+    wide_tile: int = 256         # H2O3_WIDE_TILE: 128, the 128-tile fused Gram kernel
+    wide_slices: int = 0         # H2O3_WIDE_SLICES: row slices per tile pair (0: fill the chip)
+    wide_eta_blocks: int = 0     # H2O3_WIDE_ETA_BLOCKS: grid of the wide eta pass (0: resident rounds)
+    wide_group: int = 4          # H2O3_WIDE_GROUP: row chunks per batched GEMM of the split pass
+    wide_overlap: bool = False   # H2O3_WIDE_OVERLAP: split kernels on a side stream beside the GEMM
+    gi_blocks: int = 1024        # H2O3_GI_BLOCKS: target workgroups of the narrow kernel
+
+    @classmethod
+    def from_env(cls, env=None):
+        env = os.environ if env is None else env
+        on = lambda k: env.get(k, "1") != "0"
+        num = lambda k, d: int(env.get(k, d))
+        return cls(narrow_max=num("H2O3_GLM_NARROW_MAX", 128), bf16=on("H2O3_GLM_BF16"), bf3=on("H2O3_GLM_BF3"),
+                   wide_bf16=on("H2O3_GLM_WIDE_BF16"), dev_solve=on("H2O3_GLM_DEV_SOLVE"),
+                   exact_grad=on("H2O3_GLM_EXACT_GRAD"), f64_mfma=env.get("H2O3_GLM_F64_MFMA", "1") == "1",
+                   tiers=on("H2O3_GLM_TIERS"), wide_fused=on("H2O3_GLM_WIDE_FUSED"),
+                   wide_gram=env.get("H2O3_WIDE_GRAM", "bf3"), wide_tile=num("H2O3_WIDE_TILE", 256),
+                   wide_slices=num("H2O3_WIDE_SLICES", 0), wide_eta_blocks=num("H2O3_WIDE_ETA_BLOCKS", 0),
+                   wide_group=num("H2O3_WIDE_GROUP", 4), wide_overlap=env.get("H2O3_WIDE_OVERLAP", "0") == "1",
+                   gi_blocks=num("H2O3_GI_BLOCKS", 1024))
+
+
+class IrlsRoute(NamedTuple):
+    """How a driver computes its IRLS statistics (irls_route)."""
+    kind: str            # f64 | narrow_fused | narrow_external | wide_fused | wide_split | wide_gemm | generic
+    codes: tuple = None  # (link, var) codes of the fused kernels, None on the other routes
+    grad: bool = False   # the pass returns the exact-gradient channel
+    bf16_ok: bool = False   # the plain-bf16 Hessian tier exists on this route
+    tier0: str = "f32"   # the tier a run starts at, before the first condition estimate
+    wide_eta: bool = False  # lambda_max and the deviance run on the wide eta kernel
+
+    @property
+    def narrow(self):
+        return self.kind in ("narrow_fused", "narrow_external")
+
+
+def irls_route(sw, device_type, dtype, P, Pp, codes):
+    """The route of a design of P columns padded to Pp, stored as `dtype` on
+    `device_type`; `codes`: linalg_ops.glm_fused_codes of the family / link
+    (None: no fused kernel).  Takes no tensors: a driver decides once."""
+    if device_type != "cuda":
+        # always fp64 on the host (the reference's double Gram / gradient)
+        return IrlsRoute("f64", grad=True, tier0="f64")
+    if dtype == torch.float32 and Pp % 32 == 0 and Pp <= sw.narrow_max and Pp >= P + 2:
+        if codes is None or Pp & (Pp - 1):       # the fused pass needs a power-of-two padded width
+            return IrlsRoute("narrow_external", tier0="bf3" if Pp == 128 and sw.bf3 else "f32")
+        # Hessian on the matrix cores + exact gradient channel (Pp in 32 / 64 / 128)
+        grad = linalg_ops.glm_grad_supported(Pp) and sw.exact_grad
+        # the plain-bf16 tier (glm_irls_ws_kernel LO = false) needs that channel and the bf16 MFMA path
+        bf16_ok = grad and Pp == 128 and sw.bf16 and sw.bf3
+        return IrlsRoute("narrow_fused", codes, grad, bf16_ok,
+                         ("bf16" if bf16_ok else "bf3") if Pp == 128 and sw.bf3 else "f32")
+    if Pp > sw.narrow_max and P + 2 <= 1024 and codes is not None and sw.wide_gram == "bf3":
+        # fused: eta pass + one hand-written MFMA Gram kernel over the f32 rows
+        # (needs the exact gradient: its Gram has no z column); its plain-bf16
+        # tier exists on the 256 tiles only
+        grad = sw.exact_grad
+        fused = grad and sw.wide_fused
+        bf16_ok = fused and sw.wide_bf16 and sw.wide_tile == 256
+        return IrlsRoute("wide_fused" if fused else "wide_split", codes, grad, bf16_ok,
+                         ("bf16" if bf16_ok else "bf3") if grad else "f32", sw.wide_fused)
+    return IrlsRoute("wide_gemm" if Pp > sw.narrow_max else "generic")
+
+
+class IrlsStats(NamedTuple):
+    """Sufficient statistics of one IRLS pass, before the all-reduce."""
+    G: torch.Tensor      # X'WX [P, P]
+    xz: torch.Tensor     # X'Wz [P]
+    xw: torch.Tensor     # X'W [P]
+    sw: torch.Tensor     # sum W [1]
+    swz: torch.Tensor    # sum Wz [1]
+    dev: torch.Tensor    # deviance [1]
+    grad: torch.Tensor = None    # exact-gradient channel X'r [P + 1] (sum r last)
+    grad_beta: np.ndarray = None  # the coefficients the pass (and so `grad`) was taken at
 
 
 def _native_cd():
@@ -279,6 +367,7 @@ class GLMDriver:
         self.est = est
         p = est._parms
         self.spec = spec
+        self.sw = GlmSwitches.from_env()    # read once: later changes of the environment do not reach this driver
         fam = (p.get("family") or "AUTO").lower()
         if fam == "auto":
             fam = "binomial" if spec.nclasses == 2 else ("multinomial" if spec.nclasses > 2 else "gaussian")
@@ -325,6 +414,12 @@ class GLMDriver:
         self.offset = off.to(torch.float64) if off is not None else None
         self.P = self.dinfo.P
         self.Pp = self.dinfo.Pp
+        self.route = irls_route(self.sw, self.X.device.type, self.X.dtype, self.P, self.Pp,
+                                linalg_ops.glm_fused_codes(self.fam.family, self.fam.link, self.fam.tlp))
+        self._wide_kw = dict(tile=self.sw.wide_tile, slices=self.sw.wide_slices, eta_blocks=self.sw.wide_eta_blocks,
+                             group=self.sw.wide_group, overlap=self.sw.wide_overlap)
+        self._f32 = None       # f32 casts of (y, w, offset) for the fused kernels, see _f32_inputs
+        self._pin_bufs, self._pin_i = None, 0    # pinned host buffers of _finish_stats_dev
         self.intercept = bool(p.get("intercept", True))
         self.wsum = coll.allreduce_scalar(float(self.w.sum()))
         self.nobs = coll.allreduce_scalar(float((self.w > 0).sum()))
@@ -362,7 +457,7 @@ class GLMDriver:
         if sv is not None:
             self._set_startval(sv)
         self.active = None     # collinear-column mask (remove_collinear_columns)
-        self._hprec = None     # Hessian precision tier (None: not chosen yet), see _check_tier
+        self._hprec = None     # Hessian precision tier (None: not chosen yet), see _settle_tier
         self.hessian_kappa = None
         self.iter = 0
         self.lambda_max = self._lambda_max()
@@ -512,25 +607,32 @@ class GLMDriver:
             eta = eta + self.offset
         return eta
 
+    def _f32_inputs(self):
+        """(y, prior weights, offset) as f32 for the fused kernels, cast once.
+        The narrow kernel takes None for all-ones weights, the wide one a tensor."""
+        if self._f32 is None:
+            y32 = self.y.to(torch.float32)
+            unit = self.route.narrow and bool((self.w == 1).all())
+            self._f32 = (y32, None if unit else self.w.to(torch.float32),
+                         None if self.offset is None else self.offset.to(torch.float32))
+        return self._f32
+
+    def _beta_f32(self):
+        """The coefficients as the f32 kernels see them (intercept last)."""
+        return np.concatenate([self.beta[:self.P].astype(np.float32).astype(np.float64),
+                               [float(np.float32(self.beta[-1]))]])
+
     def _wide_eta_codes(self):
         """Family codes when the wide fused eta kernel applies (the wide IRLS
-        path of _irls_stats), else None."""
-        codes = linalg_ops.glm_fused_codes(self.fam.family, self.fam.link, self.fam.tlp)
-        if self.X.device.type == "cuda" and self.Pp > _narrow_max() and self.P + 2 <= 1024 and codes is not None and \
-                linalg_ops._wide_mode() == "bf3" and linalg_ops.wide_fused_enabled():
-            if not hasattr(self, "_y32"):
-                self._y32 = self.y.to(torch.float32)
-                self._w32 = self.w.to(torch.float32)
-                self._off32 = None if self.offset is None else self.offset.to(torch.float32)
-            return codes
-        return None
+        routes), else None."""
+        return self.route.codes if self.route.wide_eta else None
 
     def _wide_eta_pass(self, codes, beta, b0):
         """(deviance, X'r) of the wide eta kernel at (beta[:P], b0): one pass
         over X instead of a GEMV plus torch elementwise passes."""
         bt = torch.as_tensor(np.asarray(beta[:self.P], dtype=np.float64), dtype=torch.float32, device=self.X.device)
-        _, dev, gx = linalg_ops.glm_wide_irls(self.X, self.P, bt, float(b0), self._y32, self._w32, self._off32,
-                                              codes, self.fam.tvp, self.fam.theta, fused=True, eta_only=True)
+        _, dev, gx = linalg_ops.glm_wide_irls(self.X, self.P, bt, float(b0), *self._f32_inputs(), codes, self.fam.tvp,
+                                              self.fam.theta, fused=True, eta_only=True, **self._wide_kw)
         return dev, gx
 
     def _lambda_max(self):
@@ -543,63 +645,44 @@ class GLMDriver:
             # channel is exactly X'r with r = w (y - mu) dmu/deta / var
             _, gx = self._wide_eta_pass(codes, np.zeros(self.P), float(e0))
             g = gx[:self.P].contiguous()
-            coll.allreduce_(g)
-            g = g * self.obj_reg
-            amax = float(g.abs().max()) if g.numel() else 0.0
-            return amax / max(1e-2, self.alpha)
-        eta0 = torch.full_like(self.y, e0)
-        if self.offset is not None:
-            eta0 = eta0 + self.offset
-        mu = self.fam.linkinv(eta0)
-        d = self.fam.dmu_deta(eta0, mu)
-        r = self.w * (self.y - mu) * d / self.fam.variance(mu)
-        if self._native():
-            # X'r rides the fused Gram pass (column P of the augmented Gram)
-            g = linalg_ops.glm_irls(self.X, aug=self.P, W=r, width=self.Pp)[0][: self.P, self.P].contiguous()
         else:
-            g = (self.X.to(torch.float64).T @ r)[: self.P]
+            eta0 = torch.full_like(self.y, e0)
+            if self.offset is not None:
+                eta0 = eta0 + self.offset
+            mu = self.fam.linkinv(eta0)
+            d = self.fam.dmu_deta(eta0, mu)
+            r = self.w * (self.y - mu) * d / self.fam.variance(mu)
+            if self.route.narrow:
+                # X'r rides the fused Gram pass (column P of the augmented Gram)
+                g = linalg_ops.glm_irls(self.X, aug=self.P, W=r, width=self.Pp, bf3=self.sw.bf3,
+                                        target_blocks=self.sw.gi_blocks)[0][: self.P, self.P].contiguous()
+            else:
+                g = (self.X.to(torch.float64).T @ r)[: self.P]
         coll.allreduce_(g)
         g = g * self.obj_reg
         amax = float(g.abs().max()) if g.numel() else 0.0
         return amax / max(1e-2, self.alpha)
 
-    def _native(self):
-        return self.X.device.type == "cuda" and self.X.dtype == torch.float32 and self.Pp % 32 == 0 and \
-            self.Pp <= _narrow_max() and self.Pp >= self.P + 2
-
-    def _irls_stats_native(self):
+    def _pass_narrow(self):
         """One fused kernel pass: eta, IRLS weights, deviance, augmented Gram."""
-        P = self.P
-        codes = linalg_ops.glm_fused_codes(self.fam.family, self.fam.link, self.fam.tlp)
-        if self.Pp & (self.Pp - 1):
-            codes = None  # fused path needs a power-of-two padded width
-        if not hasattr(self, "_y32"):
-            self._y32 = self.y.to(torch.float32)
-            self._w32 = None if bool((self.w == 1).all()) else self.w.to(torch.float32)
-            self._off32 = None if self.offset is None else self.offset.to(torch.float32)
-        self._gexact = None
-        hp = self._hprec or ("bf16" if codes is not None and self._narrow_bf16_ok() else None)
-        bf3 = None if hp is None else ("bf16" if hp == "bf16" else hp == "bf3")
+        P, rt = self.P, self.route
+        grad = gbeta = None
         with phase("glm.irls_pass"):
-            if codes is not None:
+            if rt.kind == "narrow_fused":
+                # before the first condition estimate: the plain bf16 tier when allowed, else the bf3 switch
+                hp = self._hprec or ("bf16" if rt.bf16_ok else None)
+                bf3 = self.sw.bf3 if hp is None else ("bf16" if hp == "bf16" else hp == "bf3")
                 bt = torch.zeros(self.Pp, dtype=torch.float32, device=self.X.device)
                 bt[:P] = torch.as_tensor(self.beta[:P], dtype=torch.float32)
-                if linalg_ops.glm_grad_supported(self.Pp):
-                    # Hessian on the matrix cores + exact gradient channel (Newton on
-                    # the exact gradient: see _finish_stats)
-                    Gf, dev, gx = linalg_ops.glm_irls(self.X, aug=P, beta=bt, b0=float(self.beta[-1]),
-                                                      y=self._y32, wprior=self._w32, offset=self._off32,
-                                                      codes=codes, tvp=self.fam.tvp, theta=self.fam.theta,
-                                                      width=self.Pp, grad=True, bf3=bf3,
-                                                      grad_f64=self._hprec not in (None, "bf3", "bf16"))
-                    self._gexact = torch.cat([gx[:P], gx[self.Pp:self.Pp + 1]])
-                    self._gbeta = np.concatenate([self.beta[:P].astype(np.float32).astype(np.float64),
-                                                  [float(np.float32(self.beta[-1]))]])
-                else:
-                    Gf, dev = linalg_ops.glm_irls(self.X, aug=P, beta=bt, b0=float(self.beta[-1]), y=self._y32,
-                                                  wprior=self._w32, offset=self._off32, codes=codes,
-                                                  tvp=self.fam.tvp, theta=self.fam.theta, width=self.Pp, bf3=bf3)
-                dev = dev.view(1)
+                y32, w32, off32 = self._f32_inputs()
+                # with the gradient channel: Newton on the exact gradient, see _finish_stats
+                out = linalg_ops.glm_irls(self.X, aug=P, beta=bt, b0=float(self.beta[-1]), y=y32, wprior=w32,
+                                          offset=off32, codes=rt.codes, tvp=self.fam.tvp, theta=self.fam.theta,
+                                          width=self.Pp, grad=rt.grad, bf3=bf3, target_blocks=self.sw.gi_blocks,
+                                          grad_f64=not rt.grad or self._hprec not in (None, "bf3", "bf16"))
+                Gf, dev = out[0], out[1].view(1)
+                if rt.grad:
+                    grad, gbeta = torch.cat([out[2][:P], out[2][self.Pp:self.Pp + 1]]), self._beta_f32()
             else:
                 eta = self._eta()
                 mu = self.fam.linkinv(eta)
@@ -607,10 +690,11 @@ class GLMDriver:
                 W = self.w * d * d / self.fam.variance(mu)
                 off = self.offset if self.offset is not None else 0.0
                 z = (eta - off) + (self.y - mu) / d
-                Gf, _ = linalg_ops.glm_irls(self.X, aug=P, W=W, z=z, width=self.Pp)
+                Gf, _ = linalg_ops.glm_irls(self.X, aug=P, W=W, z=z, width=self.Pp, bf3=self.sw.bf3,
+                                            target_blocks=self.sw.gi_blocks)
                 dev = (self.w * self.fam.deviance(self.y, mu)).sum().view(1)
-        return Gf[:P, :P], Gf[:P, P + 1].contiguous(), Gf[:P, P].contiguous(), Gf[P, P].view(1), \
-            Gf[P, P + 1].view(1), dev
+        return IrlsStats(Gf[:P, :P], Gf[:P, P + 1].contiguous(), Gf[:P, P].contiguous(), Gf[P, P].view(1),
+                         Gf[P, P + 1].view(1), dev, grad, gbeta)
 
     # Hessian precision tiers of the Newton step beta + H^-1 g (g from the exact
     # gradient channel): the iteration contracts at rate ~ kappa * eps(H), so the
@@ -621,19 +705,6 @@ class GLMDriver:
     # (eps ~ 1e-7) while kappa < 5e5, beyond that fp64 (the reference's Gram
     # precision, hex/gram/Gram.java:17) on the device's f64 GEMMs.
     _TIER_LIMITS = (("bf16", 32.0), ("bf3", 2e3), ("f32", 5e5), ("f64", float("inf")))
-
-    def _narrow_bf16_ok(self):
-        """The plain-bf16 Hessian tier of the P + 2 <= 128 fused kernel
-        (glm_irls_ws_kernel LO = false): needs the exact-gradient channel and
-        the bf16 MFMA path (H2O3_GLM_BF16=0 or H2O3_GLM_BF3=0 disable it)."""
-        return self.Pp == 128 and linalg_ops.glm_grad_supported(self.Pp) and \
-            os.environ.get("H2O3_GLM_BF16", "1") != "0" and os.environ.get("H2O3_GLM_BF3", "1") != "0"
-
-    def _wide_bf16_ok(self):
-        """The plain-bf16 Hessian tier exists for the fused wide Gram only
-        (H2O3_GLM_WIDE_BF16=0 disables it)."""
-        return linalg_ops.wide_fused_enabled() and os.environ.get("H2O3_GLM_WIDE_BF16", "1") != "0" and \
-            os.environ.get("H2O3_WIDE_TILE", "256") == "256"
 
     def _tier_for(self, kappa):
         for name, lim in self._TIER_LIMITS:
@@ -729,7 +800,7 @@ class GLMDriver:
         column removal or non-negativity -- those take the host solvers)."""
         p = self.est._parms
         return (self.X.device.type == "cuda" and self.P + 1 >= 256
-                and os.environ.get("H2O3_GLM_DEV_SOLVE", "1") != "0"
+                and self.sw.dev_solve
                 and self.lam * self.alpha == 0 and self.lower is None and self.upper is None
                 and self.rho is None and self.active is None and self._penalty_matrix() is None
                 and not p.get("remove_collinear_columns") and not p.get("non_negative")
@@ -740,31 +811,9 @@ class GLMDriver:
         coefficients) still get their condition estimate on the device: the
         (P+1)^2 statistics cross to the host once, after the tier check."""
         return (self.X.device.type == "cuda" and self.P + 1 >= 256
-                and os.environ.get("H2O3_GLM_DEV_SOLVE", "1") != "0"
+                and self.sw.dev_solve
                 and self.rho is None and self.active is None and self._penalty_matrix() is None
                 and not self.est._parms.get("remove_collinear_columns"))
-
-    def _check_tier_dev(self, Ga, b):
-        """_check_tier on device statistics (scaled-condition estimate on a
-        device Cholesky); recomputes the statistics on the device when the
-        tier must rise."""
-        while self._tiers_due():
-            Gn, _, _, l2 = self._system(Ga, b)
-            if l2 > 0:
-                Gn = Gn.clone()
-                Gn.diagonal()[:self.P] += l2
-            want = self._tier_raise(self._scaled_cond_dev(Gn))
-            if want is None:
-                break
-            self._sys_on_dev = True
-            try:
-                Ga, b, dev = self._irls_stats()
-            finally:
-                self._sys_on_dev = False
-            self._stats_dev = dev
-            if want == "f64":
-                break
-        return Ga, b
 
     def _step_solve_dev(self, Gn, bn, l2, L, info):
         """Ridge Newton step on the device from the factor L of Gn + ridge:
@@ -780,43 +829,30 @@ class GLMDriver:
             return float(h[1]), None
         return float(h[1]), h[2:].copy()
 
-    def _irls_stats(self):
-        self._gexact = None
-        if self._hprec == "f64" or self.X.device.type == "cpu":
-            # fp64 tier on the device, and always on the host (the reference's
-            # double Gram / gradient, hex/gram/Gram.java:17)
-            return self._irls_stats_f64()
-        if self._native():
-            G, xz, xw, sw, swz, dev = self._irls_stats_native()
-            return self._finish_stats(G, xz, xw, sw, swz, dev)
-        codes = linalg_ops.glm_fused_codes(self.fam.family, self.fam.link, self.fam.tlp)
-        if self.X.device.type == "cuda" and self.Pp > _narrow_max() and self.P + 2 <= 1024 and codes is not None and \
-                linalg_ops._wide_mode() == "bf3":
-            # one fused pass: eta + family + bf16 hi/lo split, then one bf16 GEMM
-            with phase("glm.wide_pass"):
-                if not hasattr(self, "_y32"):
-                    self._y32 = self.y.to(torch.float32)
-                    self._w32 = self.w.to(torch.float32)
-                    self._off32 = None if self.offset is None else self.offset.to(torch.float32)
-                P = self.P
-                bt = torch.as_tensor(self.beta[:P], dtype=torch.float32, device=self.X.device)
-                exact = os.environ.get("H2O3_GLM_EXACT_GRAD", "1") != "0"
-                # fused: eta pass + one hand-written MFMA Gram kernel over the f32
-                # rows (needs the exact gradient: its Gram has no z column)
-                fused = exact and linalg_ops.wide_fused_enabled()
-                # before the first condition estimate the fused path starts at the
-                # plain bf16 Hessian tier when allowed (raised at iteration 1 if kappa says so)
-                hp = self._hprec or ("bf16" if fused and self._wide_bf16_ok() else "bf3")
-                Gf, dev, gx = linalg_ops.glm_wide_irls(self.X, P, bt, float(self.beta[-1]), self._y32,
-                                                       self._w32, self._off32, codes, self.fam.tvp, self.fam.theta,
-                                                       fused=fused, bf3=hp != "bf16")
-                if exact:
-                    self._gexact = gx[:P + 1]
-                    self._gbeta = np.concatenate([self.beta[:P].astype(np.float32).astype(np.float64),
-                                                  [float(np.float32(self.beta[-1]))]])
-            with phase("glm.finish"):
-                return self._finish_stats(Gf[:P, :P], Gf[:P, P + 1].contiguous(), Gf[:P, P].contiguous(),
-                                          Gf[P, P].view(1), Gf[P, P + 1].view(1), dev.view(1))
+    def _irls_stats(self, on_dev=False):
+        """(Gram, right-hand side, deviance) of the IRLS system at self.beta by
+        this driver's route; the fp64 tier overrides every route."""
+        kind = "f64" if self._hprec == "f64" else self.route.kind
+        return self._finish_stats(self._PASSES[kind](self), on_dev)
+
+    def _pass_wide(self):
+        """One fused pass: eta + family (+ bf16 hi/lo split, then one bf16
+        GEMM, on the wide_split route)."""
+        P, rt = self.P, self.route
+        with phase("glm.wide_pass"):
+            bt = torch.as_tensor(self.beta[:P], dtype=torch.float32, device=self.X.device)
+            # before the first condition estimate the fused pass starts at the
+            # plain bf16 Hessian tier when allowed (raised at iteration 1 if kappa says so)
+            hp = self._hprec or ("bf16" if rt.bf16_ok else "bf3")
+            Gf, dev, gx = linalg_ops.glm_wide_irls(self.X, P, bt, float(self.beta[-1]), *self._f32_inputs(), rt.codes,
+                                                   self.fam.tvp, self.fam.theta, fused=rt.kind == "wide_fused",
+                                                   bf3=hp != "bf16", **self._wide_kw)
+        return IrlsStats(Gf[:P, :P], Gf[:P, P + 1].contiguous(), Gf[:P, P].contiguous(), Gf[P, P].view(1),
+                         Gf[P, P + 1].view(1), dev.view(1), *((gx[:P + 1], self._beta_f32()) if rt.grad else ()))
+
+    def _pass_torch(self):
+        """Elementwise torch passes, then the Gram: the split + GEMM augmented
+        Gram (wide_gemm route, non-negative weights) or weighted_gram + GEMVs."""
         with phase("glm.eta"):
             eta = self._eta()
         with phase("glm.weights"):
@@ -830,11 +866,13 @@ class GLMDriver:
                 W = self.w
                 z = self.y - off
             Wf = W.to(torch.float32)
-        if self.X.device.type == "cuda" and self.Pp > _narrow_max() and bool((W >= 0).all()):
+        if self.route.kind == "wide_gemm" and bool((W >= 0).all()):
             with phase("glm.gram"):
-                G, xw, xz, sw, swz = linalg_ops.weighted_gram_aug(self.X, W, z, self.P)
+                G, xw, xz, sw, swz = linalg_ops.weighted_gram_aug(self.X, W, z, self.P, mode=self.sw.wide_gram,
+                                                                  group=self.sw.wide_group,
+                                                                  overlap=self.sw.wide_overlap)
                 dev = (self.w * self.fam.deviance(self.y, mu)).sum().view(1)
-            return self._finish_stats(G, xz, xw, sw.view(1), swz.view(1), dev)
+            return IrlsStats(G, xz, xw, sw.view(1), swz.view(1), dev)
         with phase("glm.gram"):
             G = linalg_ops.weighted_gram(self.X, Wf)[: self.P, : self.P]
         with phase("glm.xtwz"):
@@ -845,9 +883,9 @@ class GLMDriver:
             xw = (self.X.T @ Wf).to(torch.float64)[: self.P]
             sw, swz = W.sum().view(1), Wz.sum().view(1)
             dev = (self.w * self.fam.deviance(self.y, mu)).sum().view(1)
-        return self._finish_stats(G, xz, xw, sw, swz, dev)
+        return IrlsStats(G, xz, xw, sw, swz, dev)
 
-    def _irls_stats_f64(self, step=1 << 21):
+    def _pass_f64(self, step=1 << 21):
         """fp64 IRLS statistics on the device (chunked f64 GEMMs): Gram,
         exact gradient X'r (r = w (y - mu) dmu/deta / var) and deviance at the
         f64 coefficients.  The top precision tier for ill-conditioned designs."""
@@ -860,7 +898,7 @@ class GLMDriver:
         dev = torch.zeros(1, dtype=torch.float64, device=dv)
         ident = self.fam.family == "gaussian" and self.fam.link == "identity"
         native = (X.is_cuda and X.dtype == torch.float32 and X.stride(1) == 1
-                  and os.environ.get("H2O3_GLM_F64_MFMA", "1") == "1")
+                  and self.sw.f64_mfma)
         with phase("glm.irls_f64"):
             for a in range(0, X.shape[0], step):
                 if native:
@@ -891,29 +929,31 @@ class GLMDriver:
                     Ga += (Xa * W.view(-1, 1)).T @ Xa
                     g += Xa.T @ r
                 dev += (w * self.fam.deviance(y, mu)).sum()
-        self._gexact = g
-        self._gbeta = self.beta.copy()
         z = torch.zeros(P, dtype=torch.float64, device=dv)
-        return self._finish_stats(Ga[:P, :P], z, Ga[:P, P].contiguous(), Ga[P, P].view(1),
-                                  torch.zeros(1, dtype=torch.float64, device=dv), dev)
+        return IrlsStats(Ga[:P, :P], z, Ga[:P, P].contiguous(), Ga[P, P].view(1),
+                         torch.zeros(1, dtype=torch.float64, device=dv), dev, g, self.beta.copy())
 
-    def _finish_stats(self, G, xz, xw, sw, swz, dev):
-        """All-reduce the IRLS sufficient statistics; returns (Gram [P+1, P+1]
-        with the intercept last, right-hand side b, deviance).
+    _PASSES = {"f64": _pass_f64, "narrow_fused": _pass_narrow, "narrow_external": _pass_narrow,
+               "wide_fused": _pass_wide, "wide_split": _pass_wide, "wide_gemm": _pass_torch, "generic": _pass_torch}
 
-        With the exact-gradient channel (self._gexact = X'r, r = w (y - mu)
-        dmu/deta / var, at the f32 coefficients the kernel used) the
+    def _finish_stats(self, st, on_dev=False):
+        """All-reduce the IRLS sufficient statistics `st`; returns (Gram
+        [P+1, P+1] with the intercept last, right-hand side b, deviance).
+        on_dev: device statistics stay there as tensors (step -> _step_dev).
+
+        With the exact-gradient channel (st.grad = X'r, r = w (y - mu)
+        dmu/deta / var, at the coefficients st.grad_beta the kernel used) the
         right-hand side is G beta_f + g instead of the Gram's own X'Wz column:
         identical in exact arithmetic (X'Wz = X'W eta + X'r), but the solve is
         then a Newton step on an exact gradient, whose fixed point g = 0 does
         not depend on the precision of the bf16x3 Hessian."""
-        gx = getattr(self, "_gexact", None)
-        parts = [G.reshape(-1), xz, xw, sw, swz, dev] + ([gx] if gx is not None else [])
-        stats = torch.cat([t.reshape(-1).to(torch.float64) for t in parts])
-        coll.allreduce_(stats)
-        P = self.P
-        if stats.is_cuda:
-            return self._finish_stats_dev(stats, gx is not None)
+        parts = [t for t in st[:7] if t is not None]
+        with phase("glm.finish"):
+            stats = torch.cat([t.reshape(-1).to(torch.float64) for t in parts])
+            coll.allreduce_(stats)
+            P = self.P
+            if stats.is_cuda:
+                return self._finish_stats_dev(stats, st.grad_beta, on_dev)
         host = stats.cpu().numpy()               # one device -> host copy
         o = 0
         G = host[o:o + P * P].reshape(P, P); o += P * P
@@ -924,14 +964,14 @@ class GLMDriver:
         Ga[:P, :P] = G
         Ga[:P, P] = Ga[P, :P] = xw
         Ga[P, P] = sw
-        if gx is not None:
+        if st.grad is not None:
             g = host[o:o + P + 1]
-            b = Ga @ self._gbeta + g
+            b = Ga @ st.grad_beta + g
         else:
             b = np.concatenate([xz, [swz]])
         return Ga, b, dev
 
-    def _finish_stats_dev(self, stats, exact):
+    def _finish_stats_dev(self, stats, grad_beta, on_dev):
         """_finish_stats for device statistics: the (P+1)^2 system and its
         right-hand side are assembled on the device and reach the host in ONE
         copy into a pinned buffer (two alternating buffers: a tier
@@ -949,22 +989,21 @@ class GLMDriver:
         Ga[:P, P] = xw
         Ga[P, :P] = xw
         Ga[P, P] = sw
-        if exact:
-            gb = torch.as_tensor(self._gbeta, dtype=torch.float64).to(dev_, non_blocking=True)
+        if grad_beta is not None:
+            gb = torch.as_tensor(grad_beta, dtype=torch.float64).to(dev_, non_blocking=True)
             b = Ga @ gb + stats[o:o + P + 1]
         else:
             b = torch.cat([xz, swz.view(1)])
-        if getattr(self, "_sys_on_dev", False):
+        if on_dev:
             # the system stays on the device (step -> _step_solve_dev)
             return Ga, b, float(devv)
         out = torch.cat([Ga.reshape(-1), b, devv.view(1)])
         n = out.numel()
-        bufs = getattr(self, "_pin_bufs", None)
-        if bufs is None or bufs[0].numel() < n:
-            bufs = self._pin_bufs = [torch.empty(n, dtype=torch.float64, pin_memory=True) for _ in range(2)]
+        if self._pin_bufs is None or self._pin_bufs[0].numel() < n:
+            self._pin_bufs = [torch.empty(n, dtype=torch.float64, pin_memory=True) for _ in range(2)]
             self._pin_i = 0
-        self._pin_i = getattr(self, "_pin_i", 0) ^ 1
-        host_t = bufs[self._pin_i][:n]
+        self._pin_i ^= 1
+        host_t = self._pin_bufs[self._pin_i][:n]
         host_t.copy_(out)                        # synchronous D2H into pinned memory
         host = host_t.numpy()
         m = (P + 1) * (P + 1)
@@ -995,7 +1034,7 @@ class GLMDriver:
 
     def _tiers_due(self):
         """The tier is (re)checked at iterations 1, 2, 4, 8, ... on the GPU."""
-        if self.X.device.type != "cuda" or os.environ.get("H2O3_GLM_TIERS", "1") == "0":
+        if self.X.device.type != "cuda" or not self.sw.tiers:
             return False
         it = self.iter + 1
         return not (it & (it - 1))
@@ -1006,109 +1045,98 @@ class GLMDriver:
         None."""
         self.hessian_kappa = kappa
         order = [t for t, _ in self._TIER_LIMITS]
-        wide = not self._native()
-        cur = self._hprec
-        bf16_ok = self._gexact is not None and (self._wide_bf16_ok() if wide else self._narrow_bf16_ok())
-        if cur is None:
-            ws_bf3 = self.Pp == 128 and os.environ.get("H2O3_GLM_BF3", "1") != "0"
-            cur = ("bf16" if bf16_ok else "bf3") if (ws_bf3 if not wide else self._gexact is not None) else "f32"
+        rt = self.route
+        cur = self._hprec or rt.tier0
         want = self._tier_for(kappa)
-        if want == "bf16" and not bf16_ok:
+        if want == "bf16" and not rt.bf16_ok:
             want = "bf3"
-        if want == "f32" and (wide or self._gexact is None):
+        if want == "f32" and not (rt.narrow and rt.grad):
             # no f32 path with the gradient channel here: straight to fp64
             want = "f64"
         if order.index(want) > order.index(cur):
             self._hprec = want
             return want
-        if self._hprec is None:
-            self._hprec = cur
+        self._hprec = cur
         return None
 
-    def _check_tier(self, Ga, b):
+    def _settle_tier(self, Ga, b, dev, kappa_of):
         """Hessian precision tier from the scaled condition number of this
-        iteration's system (checked at iterations 1, 2, 4, 8, ...); when the
-        tier must rise, the statistics are recomputed at the new tier."""
-        if not self._tiers_due():
-            return Ga, b
+        iteration's system (checked at iterations 1, 2, 4, 8, ...): while the
+        tier must rise, the statistics are recomputed at the new tier (where
+        the old ones were, device or host) and, below fp64, checked again.
+        kappa_of(Ga, b) -> (kappa, whatever it built of the system); returns
+        (Ga, b, dev, that of the system in hand or None)."""
+        on_dev, built = torch.is_tensor(Ga), None
+        due = self._tiers_due()
+        while due:
+            with phase("glm.tier"):
+                kappa, built = kappa_of(Ga, b)
+                want = self._tier_raise(kappa)
+            if want is None:
+                break
+            (Ga, b, dev), built = self._irls_stats(on_dev), None
+            due = want != "f64"
+        return Ga, b, dev, built
+
+    def _kappa_host(self, Ga, b):
         Gn, _, _, l2 = self._system(Ga, b)
         if l2 > 0:
             Gn = Gn.copy()
             Gn[np.arange(self.P), np.arange(self.P)] += l2
-        want = self._tier_raise(self._scaled_cond(Gn, self.active))
-        if want is not None:
-            Ga, b, dev = self._irls_stats()
-            self._stats_dev = dev
-            return self._check_tier(Ga, b) if want != "f64" else (Ga, b)
-        return Ga, b
+        return self._scaled_cond(Gn, self.active), None
+
+    def _kappa_dev(self, Ga, b):
+        """_kappa_host on device statistics (systems whose solve needs the
+        host: scaled-condition estimate on a device Cholesky)."""
+        Gn, _, _, l2 = self._system(Ga, b)
+        if l2 > 0:
+            Gn = Gn.clone()
+            Gn.diagonal()[:self.P] += l2
+        return self._scaled_cond_dev(Gn), None
+
+    def _kappa_ridge_dev(self, Ga, b):
+        """Scaled-condition estimate from the Cholesky factor that the device
+        solve then uses."""
+        sys_ = self._ridge_system_dev(Ga, b)
+        return self._kappa_from_factor(*sys_[4:]), sys_
 
     def _ridge_system_dev(self, Ga, b):
         """Device system (Gn, bn, l1, l2), A = Gn + the ridge on the
         penalized diagonal, and A's Cholesky factor."""
-        Gn, bn, l1, l2 = self._system(Ga, b)
-        A = Gn
-        if l2 != 0:
-            A = Gn.clone()
-            pen = torch.full((A.shape[0],), l2, dtype=A.dtype, device=A.device)
-            if self.intercept:
-                pen[-1] = 0.0
-            A.diagonal().add_(pen)
-        L, info = torch.linalg.cholesky_ex(A)
+        with phase("glm.system"):
+            Gn, bn, l1, l2 = self._system(Ga, b)
+            A = Gn
+            if l2 != 0:
+                A = Gn.clone()
+                pen = torch.full((A.shape[0],), l2, dtype=A.dtype, device=A.device)
+                if self.intercept:
+                    pen[-1] = 0.0
+                A.diagonal().add_(pen)
+            L, info = torch.linalg.cholesky_ex(A)
         return Gn, bn, l1, l2, A, L, info
-
-    def _step_dev(self, Ga, b):
-        """Device-resident step: ONE f64 Cholesky per system serves both the
-        tier check (scaled-condition estimate from the same factor) and the
-        Newton solve; the statistics are recomputed only when the tier rises."""
-        check = True
-        while True:
-            with phase("glm.system"):
-                Gn, bn, l1, l2, A, L, info = self._ridge_system_dev(Ga, b)
-            if not (check and self._tiers_due()):
-                break
-            with phase("glm.tier"):
-                want = self._tier_raise(self._kappa_from_factor(A, L, info))
-            if want is None:
-                break
-            self._sys_on_dev = True
-            try:
-                Ga, b, dev = self._irls_stats()
-            finally:
-                self._sys_on_dev = False
-            self._stats_dev = dev
-            check = want != "f64"
-        with phase("glm.solve"):
-            gmax, new = self._step_solve_dev(Gn, bn, l2, L, info)
-        return Gn, bn, l1, l2, gmax, new
 
     def step(self):
         """One IRLS iteration (Gram on the matrix cores + host solve; wide
         ridge-only systems are conditioned and solved on the device)."""
         dev_solve = self._dev_system_ok()
-        self._sys_on_dev = dev_solve or self._dev_tier_ok()
-        try:
-            Ga, b, dev = self._irls_stats()
-        finally:
-            self._sys_on_dev = False
-        self._stats_dev = dev
+        Ga, b, dev = self._irls_stats(dev_solve or self._dev_tier_ok())
         if torch.is_tensor(Ga) and dev_solve:
-            Gn, bn, l1, l2, gmax, new = self._step_dev(Ga, b)
+            # device-resident step: ONE f64 Cholesky per system serves both the
+            # tier check and the Newton solve (the factor of the last system)
+            Ga, b, dev, sys_ = self._settle_tier(Ga, b, dev, self._kappa_ridge_dev)
+            Gn, bn, l1, l2, _, L, info = sys_ or self._ridge_system_dev(Ga, b)
+            with phase("glm.solve"):
+                gmax, new = self._step_solve_dev(Gn, bn, l2, L, info)
             if new is not None:
-                return self._finish_step(new, gmax, self._stats_dev, l1, l2)
+                return self._finish_step(new, gmax, dev, l1, l2)
             Gn, bn = Gn.cpu().numpy(), bn.cpu().numpy()
-            dev = self._stats_dev
-        elif torch.is_tensor(Ga):
-            # l1 / bounds: condition estimate on the device, solve on the host
-            with phase("glm.tier"):
-                Ga, b = self._check_tier_dev(Ga, b)
-            Ga, b = Ga.cpu().numpy(), b.cpu().numpy()
-            dev = self._stats_dev
-            with phase("glm.system"):
-                Gn, bn, l1, l2 = self._system(Ga, b)
         else:
-            with phase("glm.tier"):
-                Ga, b = self._check_tier(Ga, b)
-            dev = self._stats_dev
+            if torch.is_tensor(Ga):
+                # l1 / bounds: condition estimate on the device, solve on the host
+                Ga, b, dev, _ = self._settle_tier(Ga, b, dev, self._kappa_dev)
+                Ga, b = Ga.cpu().numpy(), b.cpu().numpy()
+            else:
+                Ga, b, dev, _ = self._settle_tier(Ga, b, dev, self._kappa_host)
             with phase("glm.system"):
                 Gn, bn, l1, l2 = self._system(Ga, b)
         if self.est._parms.get("remove_collinear_columns") and self.active is None:

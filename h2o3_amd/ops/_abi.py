@@ -42,7 +42,7 @@ _TABLE = {
     "gram": """
         h2o_gram                 i  PPqiPiiiPP
         h2o_glm_irls_chunk       i  i
-        h2o_glm_irls             i  PqiiPiiiPfPPPiiffPPiiPPPiiP
+        h2o_glm_irls             i  PqiiPiiiPfPPPiiffPPiiPPPiiiP
         h2o_gram_split           i  PiiiPPqPP
         h2o_glm_wide_split_grid  i  i
         h2o_glm_wide_split       i  PiiiqPfPPPiiffPPiPPP

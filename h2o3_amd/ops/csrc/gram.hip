@@ -1014,22 +1014,6 @@ static void gi_launch(bool fused, dim3 grid, hipStream_t s, const float* X, long
                      wprior, offset, fam, Wext, zext, aug, out, dev_out);
 }
 
-// H2O3_GLM_BF3: 1 (default) bf16x3 MFMA for the P = 128 ws path, 0 f32 MFMA
-// (read per call: one getenv per IRLS pass; a caller's bf3 >= 0 overrides it)
-static int gi_bf3() {
-  const char* e = getenv("H2O3_GLM_BF3");
-  return e ? atoi(e) : 1;
-}
-
-static int gi_dbg() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("H2O3_GI_DBG");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
-
 // rows_per_block must be a multiple of h2o_glm_irls_chunk(P).
 extern "C" int h2o_glm_irls_chunk(int P) {
   const int r = (8192 / P) / 4 * 4;
@@ -1040,9 +1024,9 @@ extern "C" int h2o_glm_irls(const float* X, long long N, int P, int ldx, const i
                             int rows_per_block, const float* beta, float b0, const float* y, const float* wprior,
                             const float* offset, int link, int var, float tvp, float theta, const float* Wext,
                             const float* zext, int aug, int signed_w, double* out, double* dev_out,
-                            double* grad_out, int bf3, int grad_f64, hipStream_t s) {
+                            double* grad_out, int bf3, int grad_f64, int dbg, hipStream_t s) {
   if (N <= 0 || n_pairs <= 0) return 0;
-  if (P % 32 != 0 || P > 512) return -1;
+  if (P % 32 != 0 || P > 512 || bf3 < 0 || bf3 > 2) return -1;
   // narrow row storage (ldx < P) only on the warp-specialised path
   if (ldx % 4 != 0 || ldx > P || (ldx < P && (P > 128 || (P & (P - 1)) != 0))) return -5;
   if (aug >= 0 && aug + 1 >= P) return -2;
@@ -1050,7 +1034,7 @@ extern "C" int h2o_glm_irls(const float* X, long long N, int P, int ldx, const i
   if (rows_per_block % h2o_glm_irls_chunk(P) != 0) return -4;
   const int groups = (n_pairs + 4 * GI_PPW - 1) / (4 * GI_PPW);
   dim3 grid(n_splits, groups);
-  GlmFamArgs fam{link, var, tvp, theta, gi_dbg(), signed_w, bf3 < 0 ? gi_bf3() : bf3, grad_f64};
+  GlmFamArgs fam{link, var, tvp, theta, dbg, signed_w, bf3, grad_f64};
   if (fam.bf3 == 2 && !grad_out) fam.bf3 = 1;   // the plain-bf16 Hessian only beside the exact gradient
   const bool fused = beta != nullptr;
   // the exact-gradient channel rides the fused ws kernel (P <= 128, power of
@@ -1297,9 +1281,6 @@ extern "C" int h2o_glm_wide_split_grid(int Pa) {
 }
 
 // Pa <= 1024 (P <= 1022), Pa % 4 == 0; dev_out holds `blocks` doubles.
-#ifndef WIDE_RW
-#define WIDE_RW 1
-#endif
 extern "C" int h2o_glm_wide_split(const float* X, int ldx, int P, int Pa, long long rows, const float* beta, float b0,
                                   const float* y, const float* wprior, const float* offset, int link, int var,
                                   float tvp, float theta, void* HL, double* dev_out, int blocks, double* grad_out,
@@ -1316,17 +1297,14 @@ extern "C" int h2o_glm_wide_split(const float* X, int ldx, int P, int Pa, long l
     else if (Pa <= 1024) WIDE_SPLIT(4, 2, true);
     else return -2;
   } else {
-    // weight-only pass of the fused wide IRLS: rows in flight per wave
-    // (H2O3_WIDE_RW = 1 / 2 / 4, default WIDE_RW; at 12.5M x 1000 the pass
-    // takes 10.5 / 12.5 / 12.4 ms: more rows per wave lowers occupancy
-    // (129 -> 155 -> 195 VGPRs) and does not raise the read rate)
-    static const int rw = getenv("H2O3_WIDE_RW") ? atoi(getenv("H2O3_WIDE_RW")) : WIDE_RW;
+    // weight-only pass of the fused wide IRLS: one row in flight per wave
+    // (2 / 4 rows were measured at 12.5M x 1000: 12.5 / 12.4 ms against
+    // 10.5 ms: more rows per wave lowers occupancy (129 -> 155 -> 195 VGPRs)
+    // and does not raise the read rate)
     if (Pa <= 256) WIDE_SPLIT(1, 1, false);
     else if (Pa <= 512) WIDE_SPLIT(2, 1, false);
-    else if (Pa > 1024) return -2;
-    else if (rw == 1) WIDE_SPLIT(4, 1, false);
-    else if (rw == 4) WIDE_SPLIT(4, 4, false);
-    else WIDE_SPLIT(4, 2, false);
+    else if (Pa <= 1024) WIDE_SPLIT(4, 1, false);
+    else return -2;
   }
 #undef WIDE_SPLIT
   return (int)hipGetLastError();
@@ -1536,21 +1514,19 @@ extern "C" int h2o_glm_wide_gram(const float* X, int ldx, int P, long long N, co
 // upper-right one).
 // ---------------------------------------------------------------------------
 #define WG2_T 256
-// KR rows per chunk: 32 for bf16x3 (4 planes per buffer), 32 or 64 for the
+// KR rows per chunk: 32 for bf16x3 (4 planes per buffer), 64 for the
 // one-MFMA bf16 tier (2 planes; 64 halves the barriers and weight loads per
-// row).  k-blocks of 8 are XOR-swizzled so that the 8 lanes of a b128 access
+// row: 30.4 ms against 31.6 ms at 32 rows, 12.5M x 1000).  k-blocks of 8 are XOR-swizzled so that the 8 lanes of a b128 access
 // (8 consecutive columns, one k-block) land in 8 different 16-B bank groups
 // of the 256-B bank row: pitch 64 B -> swizzle by column >> 2, pitch 128 B
 // -> by column >> 1.
-template <int KR, int SWZ = 0>
+template <int KR>
 __device__ __forceinline__ int wg2_off(int col, int kb) {
-  // SWZ (KR = 64 A/B only): 0 (col >> 1) & 7, 1 ((col >> 1) ^ (col >> 4)) & 7, 2 (col >> 2) & 7
-  const int x = KR == 32 ? (col >> 2) & 3
-                         : (SWZ == 1 ? ((col >> 1) ^ (col >> 4)) & 7 : SWZ == 2 ? (col >> 2) & 7 : (col >> 1) & 7);
+  const int x = KR == 32 ? (col >> 2) & 3 : (col >> 1) & 7;
   return col * KR + ((kb ^ x) << 3);
 }
 
-template <bool BF3, int KR, int SWZ = 0>
+template <bool BF3, int KR>
 __global__ __launch_bounds__(512, 1) void glm_wide_gram256_kernel(const float* __restrict__ X, int ldx, int P,
                                                                   long long N, const float* __restrict__ Wr, int NB,
                                                                   int npairs, int S, int fold,
@@ -1622,7 +1598,7 @@ __global__ __launch_bounds__(512, 1) void glm_wide_gram256_kernel(const float* _
       h[e] = (__bf16)x;
       if constexpr (BF3) l[e] = (__bf16)(x - (float)h[e]);
     }
-    const int off = wg2_off<KR, SWZ>(colb, rg);
+    const int off = wg2_off<KR>(colb, rg);
     *reinterpret_cast<bf16x8*>(base + (pan ? PBH : 0) * WG2_T * KR + off) = h;
     if constexpr (BF3) *reinterpret_cast<bf16x8*>(base + (pan ? 3 : 1) * WG2_T * KR + off) = l;
   };
@@ -1674,13 +1650,13 @@ __global__ __launch_bounds__(512, 1) void glm_wide_gram256_kernel(const float* _
       bf16x8 ah[4], al[4];
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
-        const int off = wg2_off<KR, SWZ>(128 * mi + 32 * a + (lane & 31), kb);
+        const int off = wg2_off<KR>(128 * mi + 32 * a + (lane & 31), kb);
         ah[a] = *reinterpret_cast<const bf16x8*>(sAh + off);
         if constexpr (BF3) al[a] = *reinterpret_cast<const bf16x8*>(sAl + off);
       }
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
-        const int off = wg2_off<KR, SWZ>(64 * nq + 32 * b + (lane & 31), kb);
+        const int off = wg2_off<KR>(64 * nq + 32 * b + (lane & 31), kb);
         const bf16x8 bh = *reinterpret_cast<const bf16x8*>(sBh + off);
 #pragma unroll
         for (int a = 0; a < 4; ++a) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh, acc[a][b], 0, 0, 0);
@@ -1735,46 +1711,22 @@ extern "C" int h2o_glm_wide_gram256(const float* X, int ldx, int P, long long N,
   if (ldx < P || S <= 0 || fold <= 0) return -1;
   const int NB = (P + 1 + WG2_T - 1) / WG2_T;
   const int npairs = NB * (NB + 1) / 2;
-  // bf16 tier chunk rows (H2O3_WIDE_KR = 32 / 64, default 64)
-  static const int kr16 = getenv("H2O3_WIDE_KR") && atoi(getenv("H2O3_WIDE_KR")) == 32 ? 32 : 64;
-  const int KR = bf3 ? 32 : kr16;
+  const int KR = bf3 ? 32 : 64;
   const size_t lds = 2 * (size_t)(bf3 ? 4 : 2) * WG2_T * KR * sizeof(__bf16);
   static bool attr = false;
   if (!attr) {
-    const size_t l3 = 2 * 4 * WG2_T * 32 * sizeof(__bf16);
-    const size_t l32 = 2 * 2 * WG2_T * 32 * sizeof(__bf16);
-    const size_t l64 = 2 * 2 * WG2_T * 64 * sizeof(__bf16);
     (void)hipFuncSetAttribute((const void*)glm_wide_gram256_kernel<true, 32>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3);
-    (void)hipFuncSetAttribute((const void*)glm_wide_gram256_kernel<false, 32>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)l32);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * 4 * WG2_T * 32 * sizeof(__bf16)));
     (void)hipFuncSetAttribute((const void*)glm_wide_gram256_kernel<false, 64>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)l64);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * 2 * WG2_T * 64 * sizeof(__bf16)));
     attr = true;
   }
   if (bf3)
     hipLaunchKernelGGL((glm_wide_gram256_kernel<true, 32>), dim3(npairs * S), dim3(512), lds, s, X, ldx, P, N, Wr, NB,
                        npairs, S, fold, part, dbg);
-  else if (KR == 32)
-    hipLaunchKernelGGL((glm_wide_gram256_kernel<false, 32>), dim3(npairs * S), dim3(512), lds, s, X, ldx, P, N, Wr,
+  else
+    hipLaunchKernelGGL((glm_wide_gram256_kernel<false, 64>), dim3(npairs * S), dim3(512), lds, s, X, ldx, P, N, Wr,
                        NB, npairs, S, fold, part, dbg);
-  else {
-    static const int swz = getenv("H2O3_WG2_SWZ") ? atoi(getenv("H2O3_WG2_SWZ")) : 0;   // A/B knob
-    if (swz == 1) {
-      (void)hipFuncSetAttribute((const void*)glm_wide_gram256_kernel<false, 64, 1>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((glm_wide_gram256_kernel<false, 64, 1>), dim3(npairs * S), dim3(512), lds, s, X, ldx, P, N,
-                         Wr, NB, npairs, S, fold, part, dbg);
-    } else if (swz == 2) {
-      (void)hipFuncSetAttribute((const void*)glm_wide_gram256_kernel<false, 64, 2>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((glm_wide_gram256_kernel<false, 64, 2>), dim3(npairs * S), dim3(512), lds, s, X, ldx, P, N,
-                         Wr, NB, npairs, S, fold, part, dbg);
-    } else {
-      hipLaunchKernelGGL((glm_wide_gram256_kernel<false, 64>), dim3(npairs * S), dim3(512), lds, s, X, ldx, P, N, Wr,
-                         NB, npairs, S, fold, part, dbg);
-    }
-  }
   return (int)hipGetLastError();
 }
 

@@ -6,7 +6,6 @@ f32-MFMA kernel (ops/csrc/gram.hip) on GPU, torch float64 on CPU.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
@@ -57,7 +56,8 @@ def _f32(t):
 
 
 def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, codes=(0, 0), tvp=0.0, theta=1e-10,
-             W=None, z=None, signed=None, target_blocks=1024, width=None, grad=False, bf3=None, grad_f64=True):
+             W=None, z=None, signed=None, target_blocks=1024, width=None, grad=False, bf3=True, grad_f64=True,
+             dbg=0):
     """One pass of the fused IRLS kernel (ops/csrc/gram.hip glm_irls_kernel).
 
     Fused mode (beta given): per row eta = x.beta + b0 + offset, the family's
@@ -72,8 +72,9 @@ def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, cod
     (exact f64 products of the f32 values, f64 sums -- or, grad_f64=False,
     f32 products summed over a lane's rows of a chunk, f64 beyond; g[Pp] =
     sum r) as a third element.
-    `bf3`: override H2O3_GLM_BF3 for this call (False: f32 MFMA Gram;
-    "bf16": one bf16 MFMA per product, fused passes with grad=True only).
+    `bf3` (Pp = 128 ws path): True bf16x3 MFMA Gram, False f32 MFMA, "bf16"
+    one bf16 MFMA per product (fused passes with grad=True only).
+    `dbg` (microbenchmarks): bit 0 skips the MFMAs, bit 1 the row loads.
     """
     N, ldx = X.shape
     P = int(width) if width else ldx
@@ -84,7 +85,6 @@ def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, cod
     pairs_t, pr = _pairs(T, X.device)
     npairs = len(pr)
     groups = -(-npairs // 36)
-    target_blocks = int(os.environ.get("H2O3_GI_BLOCKS", target_blocks))   # A/B knob
     splits = max(1, min(max(1, target_blocks // groups), N // 4096))
     rpb = -(-N // splits)
     rc = lib.h2o_glm_irls_chunk(P)
@@ -101,9 +101,8 @@ def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, cod
     rc = lib.h2o_glm_irls(_ptr(X), N, P, ldx, _ptr(pairs_t), npairs, splits, rpb, _ptr(bt), float(b0),
                           _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), int(codes[0]), int(codes[1]), float(tvp),
                           float(theta), _ptr(keep[3]), _ptr(keep[4]), int(aug), int(bool(signed)), _ptr(out),
-                          _ptr(dev), _ptr(gout), -1 if bf3 is None else (2 if bf3 == "bf16" else int(bool(bf3))),
-                          int(bool(grad_f64)),
-                          _stream())
+                          _ptr(dev), _ptr(gout), 2 if bf3 == "bf16" else int(bool(bf3)), int(bool(grad_f64)),
+                          int(dbg), _stream())
     _check(rc, "h2o_glm_irls")
     G = _assemble(out.sum(0), pairs_t, T)
     if grad:
@@ -113,10 +112,8 @@ def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, cod
 
 def glm_grad_supported(width):
     """True when glm_irls(grad=True) runs at this padded width (the fused
-    warp-specialised kernel: Pp in 32 / 64 / 128).  H2O3_GLM_EXACT_GRAD=0
-    turns the channel off (A/B only: the IRLS right-hand side then comes from
-    the Gram's own X'Wz column)."""
-    return int(width) in (32, 64, 128) and os.environ.get("H2O3_GLM_EXACT_GRAD", "1") != "0"
+    warp-specialised kernel: Pp in 32 / 64 / 128)."""
+    return int(width) in (32, 64, 128)
 
 
 def glm_irls_reference(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, fam=None, W=None, z=None):
@@ -273,13 +270,12 @@ def xtr_f64(X: torch.Tensor, P: int, r: torch.Tensor) -> torch.Tensor:
     return part.sum(0)
 
 
-# Row chunks per batched Gram GEMM: C_b = hi_b^T [hi_b | lo_b] for g chunks of
-# 512K rows in ONE strided-batched bf16 GEMM (f32 out, each chunk's f32
-# accumulation stays 512K rows long; chunks summed in f64).  One GEMM per
+# Row chunks per batched Gram GEMM (`group`): C_b = hi_b^T [hi_b | lo_b] for g
+# chunks of 512K rows in ONE strided-batched bf16 GEMM (f32 out, each chunk's
+# f32 accumulation stays 512K rows long; chunks summed in f64).  One GEMM per
 # chunk has only 4 x 8 output tiles of 256 x 256 -- scripts/glm_wide_bmm_mb.py
 # at 12.5M x 1024: 66.7 ms per pass per chunk vs 45.9 ms batched by 4
 # (1142 TFLOP/s bf16).
-_WIDE_GROUP = int(os.environ.get("H2O3_WIDE_GROUP", 4))
 
 
 def _gram_group(H, st, Pa, G):
@@ -292,13 +288,44 @@ def _gram_group(H, st, Pa, G):
     G += cross + cross.T
 
 
-def _overlap_ok(X, nch, grp):
-    """Split / GEMM overlap (opt-in, H2O3_WIDE_OVERLAP=1: measured slower at 12.5M x 1000, the split
-    kernels steal CUs from the GEMM -- profiles/glm_wide_overlap_ab_r4.txt); needs > 1 group of chunks."""
-    return X.device.type == "cuda" and nch > grp and os.environ.get("H2O3_WIDE_OVERLAP", "0") == "1"
+def _at(t, a, size=4):
+    """Pointer to element `a` of a contiguous 1-D tensor (null for None)."""
+    return ctypes.c_void_p(0 if t is None else t.data_ptr() + a * size)
 
 
-def _pipelined_groups(split, HL, N, st, grp, Pa, G):
+def _chunk_groups(split, X, st, Pa, group, overlap):
+    """[Pa, Pa] f64 Gram over the row chunks of X, `st` rows each, in groups
+    of `group` chunks per batched GEMM.  `split(i, x, r, hl, stream)` launches
+    the kernel that writes the [hi | lo] bf16 planes of chunk i (r rows from
+    pointer x) to pointer hl.  `overlap` (more than one group, measured slower
+    at 12.5M x 1000: the split kernels steal CUs from the GEMM --
+    profiles/glm_wide_overlap_ab_r4.txt): the pipelined variant."""
+    N, ldx = X.shape
+    nch = -(-N // st)
+    grp = min(nch, group)
+    HL = torch.empty((grp * st, 2 * Pa), dtype=torch.bfloat16, device=X.device)
+    G = torch.zeros((Pa, Pa), dtype=torch.float64, device=X.device)
+
+    def fill(i, buf, j, strm):
+        a = i * st
+        r = min(st, N - a)
+        split(i, ctypes.c_void_p(X.data_ptr() + a * ldx * 4), r, _at(buf, j * st * 2 * Pa, 2), strm)
+        if r < st:
+            buf[j * st + r:(j + 1) * st].zero_()
+
+    if overlap and X.device.type == "cuda" and nch > grp:
+        _pipelined_groups(fill, HL, nch, st, grp, Pa, G)
+        return G
+    stream = _stream()
+    for i in range(nch):
+        j = i % grp
+        fill(i, HL, j, stream)
+        if j == grp - 1 or i == nch - 1:
+            _gram_group(HL[:(j + 1) * st], st, Pa, G)
+    return G
+
+
+def _pipelined_groups(fill, HL, nch, st, grp, Pa, G):
     """Double-buffered row-chunk groups: the memory-bound split kernels of
     group g+1 run on a side stream while the compute-bound batched GEMM of
     group g runs on the current stream; events order each buffer's reuse
@@ -308,7 +335,6 @@ def _pipelined_groups(split, HL, N, st, grp, Pa, G):
     bufs = [HL, torch.empty_like(HL)]
     side.wait_stream(main)                       # inputs written on the main stream
     gemm_done = [None, None]
-    nch = -(-N // st)
     groups = [list(range(g0, min(g0 + grp, nch))) for g0 in range(0, nch, grp)]
     for gi, chunks in enumerate(groups):
         b = gi & 1
@@ -318,11 +344,7 @@ def _pipelined_groups(split, HL, N, st, grp, Pa, G):
                 side.wait_event(gemm_done[b])
             sid = ctypes.c_void_p(side.cuda_stream)
             for j, i in enumerate(chunks):
-                a = i * st
-                r = min(st, N - a)
-                split(i, a, r, buf, j, sid)
-                if r < st:
-                    buf[j * st + r:(j + 1) * st].zero_()
+                fill(i, buf, j, sid)
             ready = torch.cuda.Event()
             ready.record(side)
         main.wait_event(ready)
@@ -344,11 +366,7 @@ def _side_stream(dev):
     return _SIDE[k]
 
 
-def _wide_mode():
-    return os.environ.get("H2O3_WIDE_GRAM", "bf3")
-
-
-def gram_aug_bf3(X, W, z, P, step=1 << 19):
+def gram_aug_bf3(X, W, z, P, step=1 << 19, group=4, overlap=False):
     """Augmented Gram of sqrt(W) [X[:, :P] | 1 | z] (z may be None) as
     [Pa, Pa] f64, Pa = round_up(P + 2, 64): per row chunk one HIP pass
     (gram_split_kernel) writes [hi | lo] bf16 halves and one bf16 GEMM with
@@ -361,36 +379,11 @@ def gram_aug_bf3(X, W, z, P, step=1 << 19):
     Pa = -(-(P + 2) // 64) * 64
     W32, z32 = _f32(W), _f32(z)
     st = min(step, max(N, 1))
-    nch = -(-N // st)
-    grp = min(nch, _WIDE_GROUP)
-    HL = torch.empty((grp * st, 2 * Pa), dtype=torch.bfloat16, device=X.device)
-    G = torch.zeros((Pa, Pa), dtype=torch.float64, device=X.device)
-    stream = _stream()
-    def split(i, a, r, buf, j, strm):
-        rc = lib.h2o_gram_split(ctypes.c_void_p(X.data_ptr() + a * ldx * 4), ldx, P, Pa,
-                                ctypes.c_void_p(0 if W32 is None else W32.data_ptr() + a * 4),
-                                ctypes.c_void_p(0 if z32 is None else z32.data_ptr() + a * 4), r,
-                                ctypes.c_void_p(buf.data_ptr() + j * st * 2 * Pa * 2), strm)
-        _check(rc, "h2o_gram_split")
 
-    if _overlap_ok(X, nch, grp):
-        _pipelined_groups(split, HL, N, st, grp, Pa, G)
-        return G
-    for i, a in enumerate(range(0, N, st)):
-        r = min(st, N - a)
-        j = i % grp
-        split(i, a, r, HL, j, stream)
-        if r < st:
-            HL[j * st + r:(j + 1) * st].zero_()
-        if j == grp - 1 or i == nch - 1:
-            _gram_group(HL[:(j + 1) * st], st, Pa, G)
-    return G
+    def split(i, x, r, hl, strm):
+        _check(lib.h2o_gram_split(x, ldx, P, Pa, _at(W32, i * st), _at(z32, i * st), r, hl, strm), "h2o_gram_split")
 
-
-def wide_fused_enabled():
-    """The fused wide Gram (glm_wide_gram_kernel) is the default wide pass;
-    H2O3_GLM_WIDE_FUSED=0 selects the split + library GEMM pass."""
-    return os.environ.get("H2O3_GLM_WIDE_FUSED", "1") != "0"
+    return _chunk_groups(split, X, st, Pa, group, overlap)
 
 
 def _wide_gram_assemble(part, S, NB, P, T=128):
@@ -423,14 +416,15 @@ def _wide_gram_assemble(part, S, NB, P, T=128):
     return out
 
 
-def wide_gram(X, P, wr, stream=None, bf3=True):
+def wide_gram(X, P, wr, stream=None, bf3=True, tile=256, slices=0):
     """[X | 1]' diag(wr) [X | 1] (f64, (P + 2)^2 with a zero z column) by the
     hand-written MFMA kernel: 256 x 256 tiles (glm_wide_gram256_kernel,
-    default) or 128 x 128 (H2O3_WIDE_TILE=128, glm_wide_gram_kernel).
-    bf3=False (256 tiles): one bf16 MFMA per product instead of three."""
+    default) or 128 x 128 (tile=128, glm_wide_gram_kernel).
+    bf3=False (256 tiles): one bf16 MFMA per product instead of three.
+    `slices`: row slices per tile pair (0: enough to fill the chip)."""
     lib = _lib()
     N, ldx = X.shape
-    T = int(os.environ.get("H2O3_WIDE_TILE", 256))
+    T = int(tile)
     npad = -(-N // 64) * 64
     if wr.numel() < npad or wr.data_ptr() % 32:
         # the 256-tile kernel reads whole 64-row chunks of weights (zero past N)
@@ -441,7 +435,7 @@ def wide_gram(X, P, wr, stream=None, bf3=True):
     npairs = NB * (NB + 1) // 2
     from ..utils.timer import phase
     per_cu = 1 if T == 256 else 2
-    S = int(os.environ.get("H2O3_WIDE_SLICES", 0)) or max(1, 256 * per_cu // npairs)
+    S = int(slices) or max(1, 256 * per_cu // npairs)
     # f32 runs between f64 folds: 32K rows for bf16x3 products; the plain bf16
     # Hessian (~2^-9 per product) folds once at the end (a 500K-row f32 run adds
     # ~1e-4 relative, far below its own rounding) -- 64K atomics per workgroup
@@ -473,7 +467,7 @@ def _wide_split_grid(lib, Pa):
 
 
 def glm_wide_irls(X, P, beta, b0, y, wprior=None, offset=None, codes=(1, 1), tvp=0.0, theta=1e-10, step=1 << 19,
-                  fused=False, bf3=True, eta_only=False):
+                  fused=False, bf3=True, eta_only=False, tile=256, slices=0, eta_blocks=0, group=4, overlap=False):
     """Fused IRLS pass for wide GLMs (P + 2 <= 1024).
 
     fused=True (needs the exact-gradient channel: the Gram carries no z
@@ -489,7 +483,9 @@ def glm_wide_irls(X, P, beta, b0, y, wprior=None, offset=None, codes=(1, 1), tvp
     exact-gradient channel X'r with g[P] = sum r, r = w (y - mu) dmu/deta /
     var: f32 VALU products over <= 64 rows per lane, f64 beyond).
     eta_only (fused): the eta / deviance / gradient pass alone, G is None --
-    the deviance at a coefficient vector and X'r for lambda_max."""
+    the deviance at a coefficient vector and X'r for lambda_max.
+    `tile`, `slices`: wide_gram's; `eta_blocks`: grid of the fused eta pass
+    (0: whole resident rounds); `group`, `overlap`: _chunk_groups'."""
     lib = _lib()
     if lib is None:
         raise RuntimeError("gram extension not built (run __graft_entry__.build())")
@@ -509,7 +505,7 @@ def glm_wide_irls(X, P, beta, b0, y, wprior=None, offset=None, codes=(1, 1), tvp
         # rounds: 24 launches of 2048 workgroups took 10.5 ms at 12.5M x 1000,
         # one launch of 768 takes 8.1 ms (scripts/wide_eta_mb.py)
         st, nch = max(N, 1), 1
-        blocks = int(os.environ.get("H2O3_WIDE_ETA_BLOCKS", "0")) or _wide_split_grid(lib, Pa)
+        blocks = int(eta_blocks) or _wide_split_grid(lib, Pa)
         dev = torch.zeros((nch, blocks), dtype=torch.float64, device=X.device)
         gbuf = torch.zeros((blocks, Pa), dtype=torch.float64, device=X.device)
         # row weights, zero-padded to whole 64-row chunks (the Gram kernel
@@ -517,63 +513,46 @@ def glm_wide_irls(X, P, beta, b0, y, wprior=None, offset=None, codes=(1, 1), tvp
         wr = torch.empty(-(-N // 64) * 64, dtype=torch.float32, device=X.device)
         wr[N:].zero_()
         stream = _stream()
-        offp = lambda t, a: ctypes.c_void_p(0 if t is None else t.data_ptr() + a * 4)
         with phase("glm.wide_eta"):
             for i, a in enumerate(range(0, N, st)):
                 r = min(st, N - a)
                 rc = lib.h2o_glm_wide_split(ctypes.c_void_p(X.data_ptr() + a * ldx * 4), ldx, P, Pa, r, _ptr(bt),
-                                            float(b0), offp(keep[0], a), offp(keep[1], a), offp(keep[2], a),
+                                            float(b0), _at(keep[0], a), _at(keep[1], a), _at(keep[2], a),
                                             int(codes[0]), int(codes[1]), float(tvp), float(theta), None,
-                                            _ptr(dev[i]), blocks, _ptr(gbuf), offp(wr, a), stream)
+                                            _ptr(dev[i]), blocks, _ptr(gbuf), _at(wr, a), stream)
                 _check(rc, "h2o_glm_wide_split")
         if eta_only:
             return None, dev.sum(), gbuf.sum(0)
         with phase("glm.wide_gram"):
-            G = wide_gram(X, P, wr, stream, bf3=bf3)
+            G = wide_gram(X, P, wr, stream, bf3=bf3, tile=tile, slices=slices)
         return G, dev.sum(), gbuf.sum(0)
-    grp = min(nch, _WIDE_GROUP)
-    HL = torch.empty((grp * st, 2 * Pa), dtype=torch.bfloat16, device=X.device)
     blocks = 2048
     dev = torch.zeros((nch, blocks), dtype=torch.float64, device=X.device)
     gbuf = torch.zeros((blocks, Pa), dtype=torch.float64, device=X.device)
-    G = torch.zeros((Pa, Pa), dtype=torch.float64, device=X.device)
-    stream = _stream()
 
-    def off(t, a):
-        return ctypes.c_void_p(0 if t is None else t.data_ptr() + a * 4)
-
-    def split(i, a, r, buf, j, strm):
-        rc = lib.h2o_glm_wide_split(ctypes.c_void_p(X.data_ptr() + a * ldx * 4), ldx, P, Pa, r, _ptr(bt),
-                                    float(b0), off(keep[0], a), off(keep[1], a), off(keep[2], a), int(codes[0]),
-                                    int(codes[1]), float(tvp), float(theta),
-                                    ctypes.c_void_p(buf.data_ptr() + j * st * 2 * Pa * 2), _ptr(dev[i]), blocks,
-                                    _ptr(gbuf), None, strm)
+    def split(i, x, r, hl, strm):
+        a = i * st
+        rc = lib.h2o_glm_wide_split(x, ldx, P, Pa, r, _ptr(bt), float(b0), _at(keep[0], a), _at(keep[1], a),
+                                    _at(keep[2], a), int(codes[0]), int(codes[1]), float(tvp), float(theta), hl,
+                                    _ptr(dev[i]), blocks, _ptr(gbuf), None, strm)
         _check(rc, "h2o_glm_wide_split")
 
-    if _overlap_ok(X, nch, grp):
-        _pipelined_groups(split, HL, N, st, grp, Pa, G)
-        return G, dev.sum(), gbuf.sum(0)
-    for i, a in enumerate(range(0, N, st)):
-        r = min(st, N - a)
-        j = i % grp
-        split(i, a, r, HL, j, stream)
-        if r < st:
-            HL[j * st + r:(j + 1) * st].zero_()
-        if j == grp - 1 or i == nch - 1:
-            _gram_group(HL[:(j + 1) * st], st, Pa, G)
+    G = _chunk_groups(split, X, st, Pa, group, overlap)
     return G, dev.sum(), gbuf.sum(0)
 
 
-def weighted_gram_aug(X: torch.Tensor, W: torch.Tensor, z: torch.Tensor, P: int, step: int = 1 << 20):
+def weighted_gram_aug(X: torch.Tensor, W: torch.Tensor, z: torch.Tensor, P: int, step: int = 1 << 20, mode="bf3",
+                      group=4, overlap=False):
     """Augmented weighted Gram of [X[:, :P] | 1 | z] for wide GLMs in ONE
     library GEMM per 1M-row chunk (rocBLAS/hipBLASLt fp32, f64 accumulation):
     returns (X'WX [P,P], X'W [P], X'Wz [P], sum W, sum Wz) as f64.  The
     transposed GEMVs X'W / X'Wz on a row-major X run at a fraction of the GEMM
     rate on ROCm (~475 ms vs the Gram's ~240 ms at N=12.5M, P=1000), riding
-    them on the Gram as two extra columns costs ~0.2%."""
+    them on the Gram as two extra columns costs ~0.2%.  mode="bf3" (default,
+    GPU): the bf16 hi / lo split + bf16 GEMM of gram_aug_bf3 instead."""
     N = X.shape[0]
-    if X.device.type == "cuda" and _wide_mode() == "bf3":
-        G = gram_aug_bf3(X, W, z, P)
+    if X.device.type == "cuda" and mode == "bf3":
+        G = gram_aug_bf3(X, W, z, P, group=group, overlap=overlap)
         return G[:P, :P], G[:P, P], G[:P, P + 1], G[P, P], G[P, P + 1]
     G = torch.zeros((P + 2, P + 2), dtype=torch.float64, device=X.device)
     for a in range(0, N, step):

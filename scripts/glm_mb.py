@@ -37,14 +37,5 @@ t("gram W only", lambda: linalg_ops.glm_irls(X, W=W))
 t("torch X@beta", lambda: X @ beta)
 t("torch X.sum(0)", lambda: X.sum(0))
 if os.environ.get("DBG_SWEEP"):
-    import ctypes
-    for d in ("1", "2", "3"):
-        os.environ["H2O3_GI_DBG"] = d
-        # the library caches the env on first use -> run in a subprocess
-        import subprocess
-        code = ("import os,sys,time,torch;sys.path.insert(0,'.');from h2o3_amd.ops import linalg_ops as l;"
-                f"N={N};X=torch.zeros((N,128),device='cuda');W=torch.rand(N,device='cuda');"
-                "l.glm_irls(X,aug=100,W=W,z=W);torch.cuda.synchronize();t=time.perf_counter();"
-                "[l.glm_irls(X,aug=100,W=W,z=W) for _ in range(5)];torch.cuda.synchronize();"
-                "print('dbg', os.environ['H2O3_GI_DBG'], (time.perf_counter()-t)/5*1e3, 'ms', flush=True)")
-        subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ))
+    for d in (1, 2, 3):       # bit 0 skips the MFMAs, bit 1 the row loads
+        t(f"external W,z dbg={d}", lambda: linalg_ops.glm_irls(X, aug=P, W=W, z=W, dbg=d))

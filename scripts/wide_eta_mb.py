@@ -1,7 +1,6 @@
 """Wide GLM eta / weight / gradient pass alone (glm_wide_split_kernel in
 weight-only mode) at 12.5M x P: ms per pass and the X read rate for
-workgroup counts given on the command line (the rows-in-flight variant is
-picked by H2O3_WIDE_RW, read once per process)."""
+workgroup counts given on the command line."""
 import ctypes
 import os
 import sys
@@ -21,7 +20,6 @@ y = (torch.rand(N, device="cuda") < 0.5).float()
 wr = torch.empty(N, device="cuda")
 lib = linalg_ops._lib()
 stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-rw = os.environ.get("H2O3_WIDE_RW", "1")
 for blocks in [int(b) for b in sys.argv[1:]] or [0]:
     blocks = blocks or linalg_ops._wide_split_grid(lib, Pa)   # 0: whole resident rounds
     dev = torch.zeros(blocks, dtype=torch.float64, device="cuda")
@@ -40,4 +38,4 @@ for blocks in [int(b) for b in sys.argv[1:]] or [0]:
         run()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t) / 10 * 1e3
-    print(f"P={P} ldx={ldx} RW={rw} blocks={blocks:5d}: {ms:6.2f} ms  {N * P * 4 / ms / 1e9:5.2f} TB/s", flush=True)
+    print(f"P={P} ldx={ldx} blocks={blocks:5d}: {ms:6.2f} ms  {N * P * 4 / ms / 1e9:5.2f} TB/s", flush=True)

@@ -39,5 +39,5 @@ for T, S, dbg, bf3 in arms:
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 3
-    kr = 32 if bf3 or os.environ.get("H2O3_WIDE_KR") == "32" else 64
+    kr = 32 if bf3 else 64
     print(f"T={T} S={S:3d} dbg={dbg} bf3={bf3} KR={kr}: {ms:7.2f} ms/launch", flush=True)

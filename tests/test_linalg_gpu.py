@@ -95,18 +95,18 @@ def test_weighted_gram_aug_matches_fp64():
 
 
 @pytest.mark.parametrize("bf3", ["1", "0"])
-def test_glm_irls_bf3_elementwise(monkeypatch, bf3):
-    """P = 100 (padded 128) runs the warp-specialised kernel; H2O3_GLM_BF3
-    selects bf16x3 (hi*hi + hi*lo + lo*hi on 16x16x32 bf16 MFMA) or f32
+def test_glm_irls_bf3_elementwise(bf3):
+    """P = 100 (padded 128) runs the warp-specialised kernel; bf3 selects
+    bf16x3 (hi*hi + hi*lo + lo*hi on 16x16x32 bf16 MFMA) or f32
     16x16x4 MFMA.  Both must match fp64 entry by entry, not just at the max."""
-    monkeypatch.setenv("H2O3_GLM_BF3", bf3)
     n, P, Pp = 300_007, 100, 128
     X, beta, g = _data(n, P, Pp, seed=11)
     X[:, 7] = 3.0 + 0.01 * X[:, 7]          # near-constant column: large mean, small spread
     y = (torch.rand(n, generator=g) < torch.sigmoid(X @ beta)).float()
     fam = _Fam("binomial", "logit")
     codes = linalg_ops.glm_fused_codes("binomial", "logit")
-    Gk, dk = linalg_ops.glm_irls(X.cuda(), aug=P, beta=beta.cuda(), b0=-0.1, y=y.cuda(), codes=codes)
+    Gk, dk = linalg_ops.glm_irls(X.cuda(), aug=P, beta=beta.cuda(), b0=-0.1, y=y.cuda(), codes=codes,
+                                 bf3=bf3 == "1")
     Gr, dr = linalg_ops.glm_irls_reference(X, aug=P, beta=beta, b0=-0.1, y=y, fam=fam)
     A, B = Gk[: P + 2, : P + 2].cpu(), Gr[: P + 2, : P + 2]
     diag = B.diagonal().abs().sqrt()
@@ -435,7 +435,7 @@ def test_group_sum_matches_index_add():
 
 
 @pytest.mark.gpu
-def test_wide_split_gemm_overlap_matches_sequential(monkeypatch):
+def test_wide_split_gemm_overlap_matches_sequential():
     """Double-buffered split / GEMM pipeline (side stream for the split
     kernels) gives exactly the sequential pass's Gram and deviance."""
     n, P = 50_021, 300
@@ -445,12 +445,11 @@ def test_wide_split_gemm_overlap_matches_sequential(monkeypatch):
     y = (torch.rand(n, generator=g) < 0.4).float().cuda()
     codes = linalg_ops.glm_fused_codes("binomial", "logit")
     W = torch.rand(n, generator=g).cuda()
-    monkeypatch.setattr(linalg_ops, "_WIDE_GROUP", 2)
     out = {}
     for mode in ("0", "1"):
-        monkeypatch.setenv("H2O3_WIDE_OVERLAP", mode)
-        G, d, gx = linalg_ops.glm_wide_irls(X, P, beta, 0.1, y, None, None, codes, step=4096)
-        Ga = linalg_ops.gram_aug_bf3(X, W, y, P, step=4096)
+        kw = dict(step=4096, group=2, overlap=mode == "1")
+        G, d, gx = linalg_ops.glm_wide_irls(X, P, beta, 0.1, y, None, None, codes, **kw)
+        Ga = linalg_ops.gram_aug_bf3(X, W, y, P, **kw)
         torch.cuda.synchronize()
         out[mode] = (G.cpu(), d.cpu(), Ga.cpu(), gx.cpu())
     for a, b in zip(out["0"], out["1"]):
@@ -460,7 +459,7 @@ def test_wide_split_gemm_overlap_matches_sequential(monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("tile,bf3", [(256, True), (128, True), (256, False)])
 @pytest.mark.parametrize("n,P", [(100, 1000), (200_003, 1000), (70_001, 127), (5_000, 255), (9_000, 300)])
-def test_glm_wide_fused_gram_matches_fp64(n, P, tile, bf3, monkeypatch):
+def test_glm_wide_fused_gram_matches_fp64(n, P, tile, bf3):
     """glm_wide_gram_kernel alone: [X | 1]' W [X | 1] from the f32 rows vs
     fp64, at widths that fill 8 column tiles (P = 1000, the BASELINE wide
     config's width), exactly one tile with and without the intercept spilling
@@ -468,7 +467,6 @@ def test_glm_wide_fused_gram_matches_fp64(n, P, tile, bf3, monkeypatch):
     ragged last chunk; both tile sizes (256: the default, diagonal tiles
     skip their lower-left quarter); the one-MFMA bf16 tier (64-row chunks)
     to bf16 rounding (~2^-9 per product)."""
-    monkeypatch.setenv("H2O3_WIDE_TILE", str(tile))
     g = torch.Generator().manual_seed(n + P)
     X = torch.randn(n, P, generator=g)
     X[:, :3] *= 40.0                                # columns of very different scale
@@ -476,7 +474,7 @@ def test_glm_wide_fused_gram_matches_fp64(n, P, tile, bf3, monkeypatch):
     y = (torch.rand(n, generator=g) < 0.4).float()
     codes = linalg_ops.glm_fused_codes("binomial", "logit")
     G, _, _ = linalg_ops.glm_wide_irls(X.cuda(), P, beta.cuda(), 0.1, y.cuda(), None, None, codes, step=1 << 16,
-                                       fused=True, bf3=bf3)
+                                       fused=True, bf3=bf3, tile=tile)
     eta = X.double() @ beta.double() + 0.1
     mu = torch.sigmoid(eta)
     W = mu * (1 - mu)
