@@ -45,8 +45,6 @@ no adaptive histogram types, max_depth <= 11.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
@@ -73,7 +71,7 @@ def _libs():
 def supported(drv) -> str | None:
     """None when the GBM driver's configuration runs on the device-resident
     tree, else the reason it does not (the engine's level loop then runs)."""
-    if os.environ.get("H2O3_DEV_TREE", "1") != "1":
+    if not drv.sw.dev_tree:
         return "disabled (H2O3_DEV_TREE=0)"
     bd, gp, p = drv.bd, drv.gp, drv.est._parms
     if drv.dev.type != "cuda":
@@ -246,13 +244,19 @@ class DevTreeGBM:
         # (H2O3_LEAF_GATHER=0: the random-store scatter), and no compaction of
         # the last level (H2O3_DEV_LAST_LEVEL=0 restores it; needs the gather:
         # the scatter has no flag-aware read)
-        self.gather = os.environ.get("H2O3_LEAF_GATHER", "1") != "0" and N > 0
-        self.last_level = self.gather and os.environ.get("H2O3_DEV_LAST_LEVEL", "1") != "0"
+        self.gather = drv.sw.leaf_gather and N > 0
+        self.last_level = self.gather and drv.sw.dev_last_level
         self.lg = LeafGather(self.lh, N, D, dev) if self.gather else None
         self.slot_wb = torch.zeros(n_lvl_max, dtype=i32, device=dev)
+        # bernoulli on one rank: the sequence is captured after the first tree and replayed
+        self.use_graph = self.bern and self.W == 1 and drv.sw.dev_tree_graph
         self.graph = None
         self._hv = [None, None]
         self._k = 0
+        self._y = (drv.yb if self.bern else torch.nan_to_num(drv.yf)).contiguous().to(torch.float32)
+        # _upload's two pinned staging slots, their copy events and the device staging buffer
+        self._stg = self._stg_ev = self._dstg = None
+        self._stg_i = 0
 
     # ---------------------------------------------------------------- scales
     def _scales(self):
@@ -285,7 +289,7 @@ class DevTreeGBM:
             offs.append(n)
             n += (a.nbytes + 7) & ~7
         n = max(n, 8)
-        if getattr(self, "_stg", None) is None or self._stg[0].numel() < n:
+        if self._stg is None or self._stg[0].numel() < n:
             self._stg = [torch.empty(n, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
             self._stg_ev = [None, None]
             self._dstg = torch.empty(n, dtype=torch.uint8, device=self.dev)
@@ -429,9 +433,6 @@ class DevTreeGBM:
         """One tree: residual -> levels -> leaf values -> per-row leaf values."""
         lh, drv = self.lh, self.drv
         s = _stream()
-        y = drv.yb if self.bern else torch.nan_to_num(drv.yf)
-        if not hasattr(self, "_y"):
-            self._y = y.contiguous().to(torch.float32)
         f = drv._f[:, 0]
         _ck(lh.h2o_gbm_grad(_ptr(self._y), _ptr(f), _ptr(self.wbuf) if self.sampled else None,
                             1 if self.bern else 0, self.N, _ptr(self.pos[0]), _ptr(self.dbuf), s), "gbm_grad")
@@ -507,7 +508,7 @@ class DevTreeGBM:
             self.vmax = [1.0, float(z.abs().max())]
             self._scales()
             self._sequence()
-        elif self.W == 1 and os.environ.get("H2O3_DEV_TREE_GRAPH", "1") == "1":
+        elif self.use_graph:
             if self.graph is None:
                 # first tree eagerly (kernel attributes, lazy library state),
                 # then capture the sequence for every later tree: capture only

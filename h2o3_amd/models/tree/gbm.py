@@ -18,6 +18,8 @@ from __future__ import annotations
 import math
 import os
 import time
+from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -46,6 +48,87 @@ GBM_DEFAULTS = dict(ntrees=50, max_depth=5, min_rows=10.0, nbins=20, nbins_top_l
                     score_tree_interval=0, balance_classes=False, class_sampling_factors=None,
                     max_after_balance_size=5.0, max_confusion_matrix_size=20, in_training_checkpoints_dir=None,
                     in_training_checkpoints_tree_interval=1)
+
+
+@dataclass(frozen=True)
+class GbmSwitches:
+    """The A/B switches of the GBM boosting path, one field per H2O3_* variable
+    (named beside it).  A GBMDriver reads them once, at construction."""
+    dev_tree: bool = True         # H2O3_DEV_TREE: the device-resident tree (devtree.py) where it is supported
+    dev_tree_graph: bool = True   # H2O3_DEV_TREE_GRAPH: its kernel sequence replayed from a captured graph
+    leaf_gather: bool = True      # H2O3_LEAF_GATHER: its per-row leaf values by the sorted-segment gather
+    dev_last_level: bool = True   # H2O3_DEV_LAST_LEVEL: its last level is not compacted (needs the gather)
+    pos_leaf: bool = True         # H2O3_POS_LEAF: leaf sums from the position-ordered payload, device values
+    gbm_grad: bool = True         # H2O3_GBM_GRAD: the residual kernel writes the grower's root payload
+    leaf_scatter: bool = True     # H2O3_LEAF_SCATTER: write-only per-row leaf values, folded in by the next tree
+
+    @classmethod
+    def from_env(cls, env=None):
+        env = os.environ if env is None else env
+        is1 = lambda k: env.get(k, "1") == "1"
+        not0 = lambda k: env.get(k, "1") != "0"
+        return cls(dev_tree=is1("H2O3_DEV_TREE"), dev_tree_graph=is1("H2O3_DEV_TREE_GRAPH"),
+                   leaf_gather=not0("H2O3_LEAF_GATHER"), dev_last_level=not0("H2O3_DEV_LAST_LEVEL"),
+                   pos_leaf=is1("H2O3_POS_LEAF"), gbm_grad=is1("H2O3_GBM_GRAD"),
+                   leaf_scatter=is1("H2O3_LEAF_SCATTER"))
+
+
+class GbmRoute(NamedTuple):
+    """How a driver grows the trees of an iteration and sets their leaf values (gbm_route)."""
+    # devtree    the device-resident tree of devtree.py
+    # onepass    level loop; kernel residual into the grower's payload, device leaf values
+    # posleaf    level loop; torch residual, device leaf values
+    # leaf_pass  level loop; device sums, host leaf values (monotone bounds, prediction noise)
+    # host       level loop; _gamma on per-row leaf ids
+    # multi_dev  K class trees on the payload path, device leaf values, one host copy per iteration
+    # multi_host K class trees, host leaf values
+    kind: str
+    devtree_why: str = None   # why the device-resident tree does not serve (None on `devtree`)
+
+
+def gbm_route(sw, device_type, K, family, link, mono_on, noise_bw, base_unit, payload_ok, devtree_why):
+    """The route of a driver: `base_unit`, every row weight is 0 or 1;
+    `payload_ok`, TreeGrower.pos_payload_ok(); `devtree_why`, the answer of
+    devtree.supported.  Takes no tensors: a driver decides once."""
+    cuda = device_type == "cuda"
+    if K > 1:
+        dev = cuda and base_unit and noise_bw == 0 and payload_ok and sw.pos_leaf
+        return GbmRoute("multi_dev" if dev else "multi_host", devtree_why)
+    if devtree_why is None:
+        return GbmRoute("devtree")
+    if not (cuda and family in ("gaussian", "bernoulli") and link in ("identity", "logit")):
+        return GbmRoute("host", devtree_why)
+    # monotone bounds / prediction noise need the leaf values on the host
+    # before the prediction update: not the device-resident leaf values
+    if mono_on or noise_bw != 0 or not sw.pos_leaf:
+        return GbmRoute("leaf_pass", devtree_why)
+    return GbmRoute("onepass" if base_unit and payload_ok and sw.gbm_grad else "posleaf", devtree_why)
+
+
+def _ratio_dev(num, den, above=None):
+    """num / den per leaf on the device, 0 where den is 0 (`above` given: where den <= above)."""
+    ok = den != 0 if above is None else den > above
+    return torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den))
+
+
+def _ratio_host(num, den, above=None):
+    """_ratio_dev on host arrays."""
+    ok = den != 0 if above is None else den > above
+    return np.where(ok, num / np.where(ok, den, 1), 0.0)
+
+
+def _segs_tile(st, ct, N):
+    """The leaf segments tile all N positions of the row permutation (the
+    write-only scatter then writes every row)."""
+    st = np.asarray(st, dtype=np.int64)
+    ct = np.asarray(ct, dtype=np.int64)
+    m = ct > 0
+    st, ct = st[m], ct[m]
+    if st.size == 0:
+        return False
+    o = np.argsort(st, kind="stable")
+    st, ct = st[o], ct[o]
+    return bool(st[0] == 0 and st[-1] + ct[-1] == N and (st.size == 1 or np.array_equal(st[1:], st[:-1] + ct[:-1])))
 
 
 class GBMDriver:
@@ -150,6 +233,16 @@ class GBMDriver:
         self.gen.manual_seed(self._seed() + cloud.rank())
         if self.dist.family == "huber":
             self.dist.huber_delta = None
+        # what the routes keep between trees (the `f` and `forest` properties own _f, _dpend, _forest_obj, _pending)
+        self._dbuf = None               # onepass: the buffer _dpend points at
+        self._hv_ring = [None, None]    # onepass / posleaf: pinned slots of the leaf values' host copy
+        self._devtree = None            # devtree: the DevTreeGBM, built by the first step
+        self.sw = GbmSwitches.from_env()    # read once: later changes of the environment do not reach this driver
+        self._base_unit = bool(((self.base_w == 0) | (self.base_w == 1)).all())
+        from . import devtree
+        self.route = gbm_route(self.sw, dev.type, self.K, self.dist.family, self.dist.link, self.mono_on,
+                               self.noise_bw, self._base_unit, self.grower.pos_payload_ok(), devtree.supported(self))
+        self._devtree_why = self.route.devtree_why
 
     def _seed(self):
         s = self.est._parms.get("seed", -1)
@@ -185,7 +278,7 @@ class GBMDriver:
 
     def _resolve_pending(self):
         """Fill the last tree's leaf values from its async device->host copy."""
-        pend = getattr(self, "_pending", None)
+        pend = self._pending
         if pend is None:
             return
         self._pending = None
@@ -233,7 +326,7 @@ class GBMDriver:
     # the next residual pass; any other reader of f flushes them first.
     @property
     def f(self):
-        d = self.__dict__.get("_dpend")
+        d = self._dpend
         if d is not None:
             self._dpend = None
             self._f[:, 0].add_(d)
@@ -244,24 +337,23 @@ class GBMDriver:
         self._dpend = None
         self._f = v
 
-    def _scatter_ok(self, st, ct):
-        """The scatter update writes every row: only when the leaf segments
-        tile all N positions of the row permutation."""
-        if os.environ.get("H2O3_LEAF_SCATTER", "1") != "1":
-            return False
-        st = np.asarray(st, dtype=np.int64)
-        ct = np.asarray(ct, dtype=np.int64)
-        m = ct > 0
-        st, ct = st[m], ct[m]
-        if st.size == 0:
-            return False
-        o = np.argsort(st, kind="stable")
-        st, ct = st[o], ct[o]
-        return bool(st[0] == 0 and st[-1] + ct[-1] == self._f.shape[0] and
-                    (st.size == 1 or np.array_equal(st[1:], st[:-1] + ct[:-1])))
-
     def step(self):
         """One boosting iteration."""
+        lr, w, maxabs = self._tree_inputs()
+        kind = self.route.kind
+        if kind == "devtree":
+            self._step_devtree(lr, w)
+        elif kind == "multi_dev":
+            self._step_multi_dev(lr, w, maxabs)
+        elif kind == "multi_host":
+            self._step_multi_host(lr, w, maxabs)
+        else:
+            self._step_single(lr, w, maxabs)
+        self.iter += 1
+
+    def _tree_inputs(self):
+        """What every route draws or derives per tree: reseeded generators, the
+        row weights, the grower's column mask; returns (lr, w, maxabs)."""
         p = self.est._parms
         from .shared import reseed_iteration
         reseed_iteration(self, self._seed(), self.iter)
@@ -271,195 +363,145 @@ class GBMDriver:
         # annealing^(trees already built - 1) while the leaves of the next tree
         # are fitted -- the first tree uses learn_rate / annealing
         lr = self.lr * (float(p.get("learn_rate_annealing", 1.0)) ** (self.iter - 1))
-        maxabs = float(p.get("max_abs_leafnode_pred", 1.79e308))
-        if self.K == 1 and self._devtree_ok():
-            self._step_devtree(lr, w)
+        return lr, w, float(p.get("max_abs_leafnode_pred", 1.79e308))
+
+    # ---- one tree per iteration on the level loop: onepass | posleaf | leaf_pass | host
+    def _step_single(self, lr, w, maxabs):
+        on_dev = self.route.kind in ("onepass", "posleaf")
+        y = self.yb if self.spec.nclasses == 2 else torch.nan_to_num(self.yf)
+        f = self._f[:, 0]
+        z = self._residual(y, f, w)
+        tree, nid, leaves = self._grow_single(z, w)
+        zpos = self.grower.pos_payload() if on_dev else None
+        if zpos is not None:
+            self._apply_dev(tree, leaves, self._leaf_values_dev(zpos, len(leaves), lr, maxabs))
             return
-        if self.K == 1:
-            dpend = self.__dict__.get("_dpend")
-            self._dpend = None
-            f = self._f[:, 0]
-            y = self.yb if self.spec.nclasses == 2 else torch.nan_to_num(self.yf)
-            # monotone bounds / prediction noise need the leaf values on the host
-            # before the prediction update: not the device-resident leaf path
-            simple = self.dev.type == "cuda" and self.dist.family in ("gaussian", "bernoulli") and \
-                self.dist.link in ("identity", "logit") and not self.mono_on and self.noise_bw == 0
-            fused = simple and os.environ.get("H2O3_FUSED_LEAF", "0") == "1"
-            # position-ordered residual payload + segment update: no per-row leaf ids at all
-            posleaf = simple and not fused and self.K == 1 and self.f.shape[1] == 1 and \
-                os.environ.get("H2O3_POS_LEAF", "1") == "1"
-            if getattr(self, "_base_unit", None) is None:
-                bw = self.base_w
-                self._base_unit = bool(((bw == 0) | (bw == 1)).all())
-            # one-pass residual straight into the grower's root payload (NaN =
-            # weight 0): the 0/1-weight position-ordered path of grow()
-            onepass = posleaf and self._base_unit and self.grower.pos_payload_ok() and \
-                os.environ.get("H2O3_GBM_GRAD", "1") == "1"
-            if dpend is not None and not onepass:
+        if on_dev:
+            # the tree kept no position-ordered payload: leaf ids and host values after all
+            nid = tree_ops.fill_nid(self.grower.ridx, *self.grower.last_segs, z.shape[0])
+        self._apply_host(tree, nid, leaves, lr * self._leaf_values_host(tree, nid, leaves, w, y, z, f, maxabs))
+
+    def _residual(self, y, f, w):
+        """The tree's response; folds the last tree's pending per-row values into f."""
+        dpend, self._dpend = self._dpend, None
+        with phase("gbm.grad"):
+            if self.route.kind == "onepass":
+                # one pass straight into the grower's root payload (NaN = weight
+                # 0): the 0/1-weight position-ordered path of grow()
+                return tree_ops.gbm_grad(y, f, None if self._unit_weights else w, self.dist.family, d=dpend)
+            if dpend is not None:
                 f.add_(dpend)
-                dpend = None
-            with phase("gbm.grad"):
-                if onepass:
-                    z = tree_ops.gbm_grad(y, f, None if self._unit_weights else w, self.dist.family, d=dpend)
-                else:
-                    z = self.dist.neg_half_gradient(y, f).to(torch.float32)
             if self.dist.family == "huber":
                 self._update_huber_delta(y, f, w)
-                z = self.dist.neg_half_gradient(y, f).to(torch.float32)
-            # bernoulli residuals y - p lie in (-1, 1): with 0/1 weights both
-            # histogram channels are bounded by 1 (no per-tree max reduction)
-            vmax_h = [1.0, 1.0] if (self.dist.family == "bernoulli" and self._base_unit) else None
-            with phase("gbm.grow"):
-                if onepass:
-                    tree, nid, leaves, tot = self.grower.grow(z, None, 0, want_nid=False, vmax=vmax_h,
-                                                              unit_w=True, va_scratch=True)
-                else:
-                    tree, nid, leaves, tot = self.grower.grow(z.contiguous(), w.contiguous(), 0,
-                                                              want_nid=not (fused or posleaf), vmax=vmax_h,
-                                                              unit_w=self._base_unit)
-            zpos = self.grower.pos_payload() if posleaf else None
-            if posleaf and zpos is None:
-                posleaf = False
-                nid = tree_ops.fill_nid(self.grower.ridx, *self.grower.last_segs, z.shape[0])
-            if posleaf:
-                # leaf values stay on the device: the prediction update runs
-                # without a host round trip and the tree's host copy of the
-                # values arrives by an async pinned copy, resolved the next time
-                # the forest is touched (no GPU bubble between trees)
+            return self.dist.neg_half_gradient(y, f).to(torch.float32)
+
+    def _grow_single(self, z, w):
+        kind = self.route.kind
+        # bernoulli residuals y - p lie in (-1, 1): with 0/1 weights both
+        # histogram channels are bounded by 1 (no per-tree max reduction)
+        vmax_h = [1.0, 1.0] if (self.dist.family == "bernoulli" and self._base_unit) else None
+        with phase("gbm.grow"):
+            if kind == "onepass":
+                tree, nid, leaves, _ = self.grower.grow(z, None, 0, want_nid=False, vmax=vmax_h, unit_w=True,
+                                                        va_scratch=True)
+            else:
+                # position-ordered residual payload + segment update: no per-row leaf ids at all
+                tree, nid, leaves, _ = self.grower.grow(z.contiguous(), w.contiguous(), 0,
+                                                        want_nid=kind != "posleaf", vmax=vmax_h,
+                                                        unit_w=self._base_unit)
+        return tree, nid, leaves
+
+    def _leaf_values_dev(self, zpos, L, lr, maxabs):
+        lids, st, ct = self.grower.last_segs
+        with phase("gbm.gamma"):
+            s_ = tree_ops.leaf_pos_sums(zpos, lids, st, ct, L, 1 if self.dist.family == "bernoulli" else 0)
+            coll.allreduce_(s_)
+            return _ratio_dev(s_[:, 0], s_[:, 1]).clamp(-maxabs, maxabs) * lr
+
+    def _apply_dev(self, tree, leaves, vals_d):
+        """The leaf values stay on the device: the prediction update runs
+        without a host round trip and the tree's host copy of the values
+        arrives by an async pinned copy, resolved the next time the forest is
+        touched (no GPU bubble between trees)."""
+        lids, st, ct = self.grower.last_segs
+        f = self._f[:, 0]
+        with phase("gbm.update"):
+            if self.route.kind == "onepass" and self.sw.leaf_scatter and _segs_tile(st, ct, f.numel()):
+                # write-only scatter of the per-row leaf value; the next
+                # residual pass adds it into f (no random read-modify-write)
+                if self._dbuf is None or self._dbuf.numel() != f.numel():
+                    self._dbuf = torch.empty_like(f)
+                tree_ops.leaf_scatter(self.grower.ridx, self._dbuf, vals_d.to(torch.float32), lids, st, ct)
+                self._dpend = self._dbuf
+            else:
+                tree_ops.leaf_update(self.grower.ridx, self._f, vals_d.to(torch.float32), lids, st, ct)
+        # two reusable pinned slots: tree t's values land in one while
+        # tree t-1's (read by _resolve_pending below) sit in the other
+        ring, k_ = self._hv_ring, self.iter & 1
+        if ring[k_] is None or ring[k_].numel() < vals_d.numel():
+            ring[k_] = torch.empty(max(vals_d.numel(), 1024), dtype=torch.float64, pin_memory=True)
+        hv = ring[k_][:vals_d.numel()]
+        hv.copy_(vals_d, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._resolve_pending()
+        self._forest_obj.add(tree, 0)
+        self._pending = (tree, list(leaves), hv, ev)
+
+    def _leaf_values_host(self, tree, nid, leaves, w, y, z, f, maxabs):
+        """Clipped (and monotone-bounded) leaf values on the host, before the learning rate."""
+        with phase("gbm.gamma"):
+            if self.route.kind == "host":
+                vals, den = self._gamma(nid, len(leaves), w, y, z, f)
+            else:
+                # gamma sums straight from the residual: den is w for gaussian and
+                # w |z| (1 - |z|) = w p (1 - p) for bernoulli -> one gather per row
                 lids, st, ct = self.grower.last_segs
-                with phase("gbm.gamma"):
-                    s_ = tree_ops.leaf_pos_sums(zpos, lids, st, ct, len(leaves),
-                                                1 if self.dist.family == "bernoulli" else 0)
-                    coll.allreduce_(s_)
-                    den = s_[:, 1]
-                    vals_d = torch.where(den != 0, s_[:, 0] / torch.where(den == 0, torch.ones_like(den), den),
-                                         torch.zeros_like(den)).clamp(-maxabs, maxabs) * lr
-                with phase("gbm.update"):
-                    if onepass and self._scatter_ok(st, ct):
-                        # write-only scatter of the per-row leaf value; the next
-                        # residual pass adds it into f (no random read-modify-write)
-                        db = self.__dict__.get("_dbuf")
-                        if db is None or db.numel() != f.numel():
-                            db = self._dbuf = torch.empty_like(f)
-                        tree_ops.leaf_scatter(self.grower.ridx, db, vals_d.to(torch.float32), lids, st, ct)
-                        self._dpend = db
-                    else:
-                        tree_ops.leaf_update(self.grower.ridx, self._f, vals_d.to(torch.float32), lids, st, ct)
-                # two reusable pinned slots: tree t's values land in one while
-                # tree t-1's (read by _resolve_pending below) sit in the other
-                ring = self.__dict__.setdefault("_hv_ring", [None, None])
-                k_ = self.iter & 1
-                if ring[k_] is None or ring[k_].numel() < vals_d.numel():
-                    ring[k_] = torch.empty(max(vals_d.numel(), 1024), dtype=torch.float64, pin_memory=True)
-                hv = ring[k_][:vals_d.numel()]
-                hv.copy_(vals_d, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                self._resolve_pending()
-                self._forest_obj.add(tree, 0)
-                self._pending = (tree, list(leaves), hv, ev)
-                self.iter += 1
-                return
-            with phase("gbm.gamma"):
-                if fused:
-                    # one walk over the leaf segments: nid fill + gamma sums
-                    lids, st, ct = self.grower.last_segs
-                    nid, s_ = tree_ops.leaf_pass(self.grower.ridx, z, w, lids, st, ct, len(leaves), z.shape[0],
-                                                 1 if self.dist.family == "bernoulli" else 0)
-                    coll.allreduce_(s_)
-                    sh = s_.cpu().numpy()
-                    vals = np.where(sh[:, 1] != 0, sh[:, 0] / np.where(sh[:, 1] == 0, 1, sh[:, 1]), 0.0)
-                elif self.dev.type == "cuda" and self.dist.family in ("gaussian", "bernoulli") and \
-                        self.dist.link in ("identity", "logit"):
-                    # gamma sums straight from the residual: den is w for gaussian and
-                    # w |z| (1 - |z|) = w p (1 - p) for bernoulli -> one gather per row
-                    lids, st, ct = self.grower.last_segs
-                    wu = None if self._unit_weights else w
-                    _, s_ = tree_ops.leaf_pass(self.grower.ridx, z, wu, lids, st, ct, len(leaves), z.shape[0],
-                                               1 if self.dist.family == "bernoulli" else 0, want_nid=False)
-                    coll.allreduce_(s_)
-                    sh = s_.cpu().numpy()
-                    vals = np.where(sh[:, 1] != 0, sh[:, 0] / np.where(sh[:, 1] == 0, 1, sh[:, 1]), 0.0)
-                    self._last_den = sh[:, 1]
-                else:
-                    self._last_den = None
-                    vals = self._gamma(tree, nid, leaves, w, y, z, f, 0)
-            vals = np.clip(vals, -maxabs, maxabs)
-            if self.mono_on:
-                from .constraints import monotone_clamp
-                dens = self._last_den if self._last_den is not None else np.asarray(tree.weight)[leaves]
-                vals = monotone_clamp(tree, leaves, vals, dens, self.gp.monotone)
-            for li, node in enumerate(leaves):
-                tree.value[node] = float(lr * vals[li])
-            with phase("gbm.update"):
-                vt = torch.tensor(lr * vals * self._noise(0, len(leaves)), dtype=torch.float32, device=self.dev)
-                if posleaf:
-                    lids, st, ct = self.grower.last_segs
-                    tree_ops.leaf_update(self.grower.ridx, self.f, vt, lids, st, ct)
-                else:
-                    self.f[:, 0] += vt[nid.long()]
-            self.forest.add(tree, 0)
-        else:
-            P = torch.softmax(self.f, 1)
-            if getattr(self, "_base_unit", None) is None:
-                bw = self.base_w
-                self._base_unit = bool(((bw == 0) | (bw == 1)).all())
-            if self.dev.type == "cuda" and self._base_unit and self.noise_bw == 0 and \
-                    self.grower.pos_payload_ok() and os.environ.get("H2O3_POS_LEAF", "1") == "1":
-                self._step_multi_dev(P, w, lr, maxabs)
-                self.iter += 1
-                return
-            new = []
-            for k in range(self.K):
-                z = (self.Y[:, k] - P[:, k]).contiguous()
-                tree, nid, leaves, tot = self.grower.grow(z, w.contiguous(), 0)
-                vals = self._gamma_multi(nid, len(leaves), w, z)
-                vals = np.clip(vals, -maxabs, maxabs)
-                for li, node in enumerate(leaves):
-                    tree.value[node] = float(lr * vals[li])
-                vt = torch.tensor(lr * vals * self._noise(k, len(leaves)), dtype=torch.float32, device=self.dev)
-                new.append(vt[nid.long()])
-                self.forest.add(tree, k)
-            for k in range(self.K):
-                self.f[:, k] += new[k]
-        self.iter += 1
+                wu = None if self._unit_weights else w
+                _, s_ = tree_ops.leaf_pass(self.grower.ridx, z, wu, lids, st, ct, len(leaves), z.shape[0],
+                                           1 if self.dist.family == "bernoulli" else 0, want_nid=False)
+                coll.allreduce_(s_)
+                sh = s_.cpu().numpy()
+                vals, den = _ratio_host(sh[:, 0], sh[:, 1]), sh[:, 1]
+        vals = np.clip(vals, -maxabs, maxabs)
+        if self.mono_on:
+            from .constraints import monotone_clamp
+            dens = den if den is not None else np.asarray(tree.weight)[leaves]
+            vals = monotone_clamp(tree, leaves, vals, dens, self.gp.monotone)
+        return vals
 
-    def _devtree_ok(self):
-        """The device-resident tree (devtree.py) serves this configuration."""
-        dt = self.__dict__.get("_devtree")
-        if dt is not None:
-            return True
-        if self.__dict__.get("_devtree_why") is not None:
-            return False
-        if getattr(self, "_base_unit", None) is None:
-            bw = self.base_w
-            self._base_unit = bool(((bw == 0) | (bw == 1)).all())
-        from . import devtree
-        why = devtree.supported(self)
-        if why is None:
-            self._devtree = devtree.DevTreeGBM(self)
-            return True
-        self._devtree_why = why
-        return False
+    def _apply_host(self, tree, nid, leaves, vals, k=0):
+        """Host leaf values (learning rate applied) into the tree and, through
+        the per-row leaf ids, into column k of f; returns nothing."""
+        for li, node in enumerate(leaves):
+            tree.value[node] = float(vals[li])
+        with phase("gbm.update"):
+            vt = torch.tensor(vals * self._noise(k, len(leaves)), dtype=torch.float32, device=self.dev)
+            self.f[:, k] += vt[nid.long()]
+        self.forest.add(tree, k)
 
-    def _step_devtree(self, lr, w=None):
+    # ---- devtree
+    def _step_devtree(self, lr, w):
         """One boosting iteration as one device-resident tree (graph replay on
         one rank): residual, every level, leaf values and the per-row leaf
         scatter without a host round trip; the tree's record is decoded on the
         host while the GPU grows the next one."""
+        if self._devtree is None:
+            # N-sized buffers: allocated by the first step, not by a driver that never steps
+            from . import devtree
+            self._devtree = devtree.DevTreeGBM(self)
         dt = self._devtree
         dt.set_tree_cols(self.gp.tree_col_mask)
         dt.set_col_sampling(self.gp.tree_col_mask)
-        pending = self.__dict__.get("_dpend") is not None
-        self._dpend = None
+        pending, self._dpend = self._dpend is not None, None
         with phase("gbm.devtree"):
             hrec, ev = dt.run(lr, pending, w)
         self._dpend = dt.dbuf
         self._resolve_pending()
         self._pending = ("dev", hrec, ev)
-        self.iter += 1
 
-    def _step_multi_dev(self, P, w, lr, maxabs):
+    # ---- K class trees per iteration: multi_dev | multi_host
+    def _step_multi_dev(self, lr, w, maxabs):
         """Multinomial iteration on the position-ordered path: each class tree
         keeps its NaN-masked residual as the grower's payload, the gamma sums
         ((K-1)/K * sum z / sum |z|(1-|z|)) come from contiguous reads of it,
@@ -467,6 +509,8 @@ class GBMDriver:
         delta -- no per-row leaf ids, no host gamma -- and ONE host copy per
         iteration brings every class tree's leaf values back."""
         K = self.K
+        P = torch.softmax(self.f, 1)
+        N = self.f.shape[0]
         wc = w.contiguous()
         deltas, vals_l, trees = [], [], []
         for k in range(K):
@@ -480,16 +524,13 @@ class GBMDriver:
             else:
                 s_ = tree_ops.seg_sum2(self.grower.ridx, wc * z, wc * z.abs() * (1 - z.abs()), lids, st, ct, L)
             coll.allreduce_(s_)
-            den = s_[:, 1]
-            v = torch.where(den > 1e-300, s_[:, 0] / torch.where(den > 1e-300, den, torch.ones_like(den)),
-                            torch.zeros_like(den))
-            v = ((K - 1.0) / K * v).clamp(-maxabs, maxabs) * lr
-            d = torch.empty(self.f.shape[0], dtype=torch.float32, device=self.dev) if self._scatter_ok(st, ct) \
-                else torch.zeros(self.f.shape[0], dtype=torch.float32, device=self.dev)
+            v = ((K - 1.0) / K * _ratio_dev(s_[:, 0], s_[:, 1], above=1e-300)).clamp(-maxabs, maxabs) * lr
             vf = v.to(torch.float32)
-            if self._scatter_ok(st, ct):
+            if self.sw.leaf_scatter and _segs_tile(st, ct, N):
+                d = torch.empty(N, dtype=torch.float32, device=self.dev)
                 tree_ops.leaf_scatter(self.grower.ridx, d, vf, lids, st, ct)
             else:
+                d = torch.zeros(N, dtype=torch.float32, device=self.dev)
                 tree_ops.leaf_update(self.grower.ridx, d, vf, lids, st, ct)
             deltas.append(d)
             vals_l.append(v)
@@ -504,6 +545,19 @@ class GBMDriver:
             o += len(leaves)
             self.forest.add(tree, k)
 
+    def _step_multi_host(self, lr, w, maxabs):
+        K = self.K
+        P = torch.softmax(self.f, 1)
+        for k in range(K):
+            z = (self.Y[:, k] - P[:, k]).contiguous()
+            tree, nid, leaves, tot = self.grower.grow(z, w.contiguous(), 0)
+            lids, st, ct = self.grower.last_segs
+            s = tree_ops.seg_sum2(self.grower.ridx, w * z, w * z.abs() * (1 - z.abs()), lids, st, ct, len(leaves))
+            coll.allreduce_(s)
+            sh = s.cpu().numpy()
+            vals = np.clip((K - 1.0) / K * _ratio_host(sh[:, 0], sh[:, 1], above=1e-300), -maxabs, maxabs)
+            self._apply_host(tree, nid, leaves, lr * vals, k)
+
     def _noise(self, k, nleaves):
         """pred_noise_bandwidth factors of this tree's leaves (1 when off)."""
         if self.noise_bw == 0:
@@ -517,13 +571,14 @@ class GBMDriver:
         m = w > 0
         self.dist.huber_delta = _weighted_quantile(r[m], w[m], self.dist.huber_alpha)
 
-    def _gamma(self, tree, nid, leaves, w, y, z, f, k):
-        L = len(leaves)
+    def _gamma(self, nid, L, w, y, z, f):
+        """Host leaf values of the distributions without device sums; returns
+        (values, the leaves' denominators or None where the rule has none)."""
         idx = nid.long()
         fam = self.dist.family
         if fam in ("laplace", "quantile"):
             alpha = 0.5 if fam == "laplace" else self.dist.quantile_alpha
-            return _segmented_wquantile(idx, (y - f).to(torch.float64), w.to(torch.float64), L, alpha)
+            return _segmented_wquantile(idx, (y - f).to(torch.float64), w.to(torch.float64), L, alpha), None
         if fam == "huber":
             res = (y - f).to(torch.float64)
             med = _segmented_wquantile(idx, res, w.to(torch.float64), L, 0.5)
@@ -536,7 +591,7 @@ class GBMDriver:
             s = torch.cat([num, den])
             coll.allreduce_(s)
             num, den = s[:L], s[L:]
-            return (mt + torch.where(den > 0, num / den.clamp_min(1e-300), torch.zeros_like(num))).cpu().numpy()
+            return (mt + torch.where(den > 0, num / den.clamp_min(1e-300), torch.zeros_like(num))).cpu().numpy(), None
         num_r = self.dist.gamma_num(w, y, z, f)
         den_r = self.dist.gamma_denom(w, y, z, f)
         lids, st, ct = self.grower.last_segs
@@ -544,20 +599,9 @@ class GBMDriver:
         coll.allreduce_(s)
         sh = s.cpu().numpy()
         num, den = sh[:, 0], sh[:, 1]
-        self._last_den = den
         if self.dist.link == "log" or self.dist.family in ("poisson", "gamma", "tweedie"):
-            return np.array([self.dist.gamma(float(a), float(b)) for a, b in zip(num, den)])
-        out = np.where(den != 0, num / np.where(den == 0, 1, den), 0.0)
-        return out
-
-    def _gamma_multi(self, nid, L, w, z):
-        K = self.K
-        lids, st, ct = self.grower.last_segs
-        s = tree_ops.seg_sum2(self.grower.ridx, w * z, w * z.abs() * (1 - z.abs()), lids, st, ct, L)
-        coll.allreduce_(s)
-        sh = s.cpu().numpy()
-        num, den = sh[:, 0], sh[:, 1]
-        return (K - 1.0) / K * np.where(den > 1e-300, num / np.where(den > 1e-300, den, 1), 0.0)
+            return np.array([self.dist.gamma(float(a), float(b)) for a, b in zip(num, den)]), den
+        return _ratio_host(num, den), den
 
     def predictions(self):
         if self.K == 1:
@@ -627,7 +671,8 @@ class H2OGradientBoostingEstimator(SharedTreeEstimator):
         self._output["init_f"] = drv.init_f
         self._train_f = drv.f
         self._vinc = None
-        self._used_devtree = drv.__dict__.get("_devtree") is not None
+        self._gbm_route = drv.route.kind
+        self._used_devtree = drv.route.kind == "devtree"
         del drv.grower
         self._driver = None
         if p.get("calibrate_model") and p.get("calibration_frame") is not None:

@@ -305,9 +305,15 @@ def test_hist_packed_single_atomic(weights):
     torch.testing.assert_close(h_gpu[..., 1], h_ref[..., 1], rtol=1e-5, atol=1e-4)
 
 
-def test_gbm_position_leaf_path_matches_nid_path(monkeypatch):
+@pytest.mark.parametrize("dev_tree", ["1", "0"])
+def test_gbm_position_leaf_path_matches_nid_path(monkeypatch, dev_tree):
     """Leaf sums from the position-ordered payload + segment f-update give the
-    same boosted model as the per-row leaf-id path."""
+    same boosted model as the per-row leaf-id path.  Every run asserts the
+    route it took (gbm.gbm_route): on the level loop (H2O3_DEV_TREE=0) the
+    three settings are three routes; with the default environment this frame
+    is served by the device-resident tree, which reads none of the two
+    variables, so that case compares the device tree with itself.  (Level
+    loop, three model seeds: the three routes differ by 6.0e-8 at most.)"""
     _need_gpu()
     import numpy as np
     import pandas as pd
@@ -321,13 +327,19 @@ def test_gbm_position_leaf_path_matches_nid_path(monkeypatch):
     df = pd.DataFrame(X, columns=[f"x{i}" for i in range(6)])
     df["y"] = np.where(y == 1, "a", "b")
     fr = h2o.H2OFrame(df)
+    monkeypatch.setenv("H2O3_DEV_TREE", dev_tree)
     preds = []
-    for flag in ("1", "0"):
-        monkeypatch.setenv("H2O3_POS_LEAF", flag)
+    for var, flag, kind in (("H2O3_POS_LEAF", "1", "onepass"), ("H2O3_POS_LEAF", "0", "leaf_pass"),
+                            ("H2O3_GBM_GRAD", "0", "posleaf")):
+        monkeypatch.delenv("H2O3_POS_LEAF", raising=False)
+        monkeypatch.delenv("H2O3_GBM_GRAD", raising=False)
+        monkeypatch.setenv(var, flag)
         m = H2OGradientBoostingEstimator(ntrees=8, max_depth=5, seed=3)
         m.train(y="y", training_frame=fr)
+        assert m._gbm_route == (kind if dev_tree == "0" else "devtree")
         preds.append(m.predict(fr).as_data_frame()["a"].values)
     np.testing.assert_allclose(preds[0], preds[1], atol=2e-5)
+    np.testing.assert_allclose(preds[0], preds[2], atol=2e-5)
 
 
 @pytest.mark.parametrize("crit", ["se", "xgb"])
@@ -727,11 +739,16 @@ def test_fill_nid_tiled_matches_reference():
 
 
 @pytest.mark.gpu
-def test_gbm_leaf_scatter_update_matches_rmw(monkeypatch):
+@pytest.mark.parametrize("dev_tree", ["1", "0"])
+def test_gbm_leaf_scatter_update_matches_rmw(monkeypatch, dev_tree):
     """The write-only leaf scatter (per-row leaf values folded into f by the
     next residual pass) trains the same model as the in-place f[ridx[p]] += v
     update, with and without row sampling (sampled-out rows are NaN-masked
-    but still tiled into leaves)."""
+    but still tiled into leaves).  Every run asserts the route it took: the
+    switch acts inside `onepass` on the level loop (H2O3_DEV_TREE=0); with
+    the default environment the device-resident tree serves this frame and
+    does not read it, so that case compares the device tree with itself.
+    (Level loop, three model seeds: the two updates give the same bits.)"""
     import numpy as np
     import torch
     import h2o3_amd as h2o
@@ -745,12 +762,14 @@ def test_gbm_leaf_scatter_update_matches_rmw(monkeypatch):
     y = (torch.rand(N, generator=g, device="cuda") < torch.sigmoid(X[:, 0] - X[:, 1])).to(torch.int32)
     fr = H2OFrame.from_vecs([Vec(X[:, j].contiguous(), T_REAL) for j in range(P)] + [Vec(y, T_ENUM, ["0", "1"])],
                             [f"x{j}" for j in range(P)] + ["y"])
+    monkeypatch.setenv("H2O3_DEV_TREE", dev_tree)
     for sr in (1.0, 0.7):
         preds = []
         for flag in ("1", "0"):
             monkeypatch.setenv("H2O3_LEAF_SCATTER", flag)
             m = H2OGradientBoostingEstimator(ntrees=6, max_depth=5, seed=3, sample_rate=sr)
             m.train(y="y", training_frame=fr)
+            assert m._gbm_route == ("onepass" if dev_tree == "0" else "devtree")
             preds.append(m.predict(fr).as_data_frame()["p1"].values)
         np.testing.assert_allclose(preds[0], preds[1], rtol=0, atol=1e-6)
 
