@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 _PREFIX = "h2o3_amd."
-_SKIP_ATTRS = {"_job", "_drv", "_lg", "_lg_key", "_pen_cache", "_graph", "_ea"}
+_SKIP_ATTRS = {"_job", "_drv", "_lg", "_lg_key", "_pen_cache", "_graph", "_ea", "_eif_sparse"}
 # estimator attributes holding per-rank ROW SHARDS as plain tensors (dim 0 =
 # this rank's rows): cross-validation holdout predictions, the GLRM row
 # representation X

@@ -14,6 +14,8 @@ GPU (forest traversal kernel for IF; batched hyperplane traversal for EIF).
 from __future__ import annotations
 
 import math
+import os
+import time
 
 import numpy as np
 import torch
@@ -56,19 +58,22 @@ def _floyd_sample(n, k, rng):
     return np.fromiter(sorted(chosen), dtype=np.int64, count=len(chosen))
 
 
-def _sample_rows(X, n, k, rng):
-    """Gather k random rows (global) of X [F, n_local] to the host."""
+def _sample_rows(X, n, k, rng, row_major=False):
+    """Gather k random rows (global) of X ([F, n_local], or [n_local, F] with
+    row_major) to the host."""
     if cloud.is_distributed():
         ntot = int(coll.allreduce_scalar(n))
     else:
         ntot = n
     idx = _floyd_sample(ntot, min(k, ntot), rng)
+
+    def take(i):
+        i = torch.as_tensor(i, device=X.device)
+        return X[i] if row_major else X[:, i].T
     if cloud.is_distributed():
         off = int(coll.all_gather_dim0(torch.tensor([n], device=X.device)).cumsum(0)[cloud.rank()].item()) - n
-        loc = idx[(idx >= off) & (idx < off + n)] - off
-        part = X[:, torch.as_tensor(loc, device=X.device)].T
-        return coll.all_gather_var(part).cpu().numpy().astype(np.float64)
-    return X[:, torch.as_tensor(idx, device=X.device)].T.cpu().numpy().astype(np.float64)
+        return coll.all_gather_var(take(idx[(idx >= off) & (idx < off + n)] - off)).cpu().numpy().astype(np.float64)
+    return take(idx).cpu().numpy().astype(np.float64)
 
 
 class H2OIsolationForestEstimator(SharedTreeEstimator):
@@ -222,12 +227,27 @@ class H2OExtendedIsolationForestEstimator(H2OEstimator):
         ext = int(p.get("extension_level", 0))
         self._psi = k
         self._height = int(math.ceil(math.log2(max(k, 2))))
-        trees = []
-        Xt = X.T.contiguous()
-        for t in range(int(p["ntrees"])):
-            S = _sample_rows(Xt, n, k, rng)
+        self._scoring_history = []
+        self._trees = trees = []
+        self._packed = None                # while None, _add_lengths packs the range it is given
+        ntrees = int(p["ntrees"])
+        every = int(p.get("score_tree_interval") or 0)
+        # score_tree_interval: a per-row total of the training frame that each
+        # tree is added to once; its last means are the training metrics'
+        tot = torch.zeros(n, dtype=torch.float64, device=X.device) if every > 0 else None
+        self._train_means = None
+        scored, start = 0, time.time()
+        for t in range(ntrees):
+            S = _sample_rows(X, n, k, rng, row_major=True)
             trees.append(self._grow(S, ext, rng))
-        self._trees = trees
+            if every > 0 and ((t + 1) % every == 0 or t + 1 == ntrees):
+                self._add_lengths(X, tot, scored, t + 1)
+                scored = t + 1
+                raw = self._raw_from_total(tot, scored)
+                self._train_means = (float(raw[:, 0].mean()), float(raw[:, 1].mean()))
+                self._scoring_history.append({
+                    "timestamp": time.time(), "duration": time.time() - start, "number_of_trees": scored,
+                    "mean_tree_path_length": self._train_means[1], "mean_anomaly_score": self._train_means[0]})
         self._pack(X.device)
         self._output["model_summary"] = {"number_of_trees": len(trees), "sample_size": k, "extension_level": ext}
 
@@ -259,11 +279,13 @@ class H2OExtendedIsolationForestEstimator(H2OEstimator):
         build(np.arange(len(S)), 0)
         return nodes
 
-    def _pack(self, dev):
+    @staticmethod
+    def _dense_pack(trees, dev):
+        """Dense [nodes, P] normal / point tables of a list of trees."""
         P = None
         normals, points, lefts, rights, vals, roots = [], [], [], [], [], []
         base = 0
-        for tr in self._trees:
+        for tr in trees:
             roots.append(base)
             for nd in tr:
                 if P is None and nd[0] is not None:
@@ -271,7 +293,7 @@ class H2OExtendedIsolationForestEstimator(H2OEstimator):
             base += len(tr)
         P = P or 1
         base = 0
-        for ti, tr in enumerate(self._trees):
+        for ti, tr in enumerate(trees):
             for nd in tr:
                 nv, pt, l, r, v = nd[:5]
                 normals.append(nv if nv is not None else np.zeros(P))
@@ -280,16 +302,28 @@ class H2OExtendedIsolationForestEstimator(H2OEstimator):
                 rights.append(r + base if r >= 0 else -1)
                 vals.append(v)
             base += len(tr)
-        self._packed = {k: torch.tensor(np.asarray(v), device=dev) for k, v in
-                        dict(normal=normals, point=points, left=lefts, right=rights, value=vals, roots=roots).items()}
+        return {k: torch.tensor(np.asarray(v), device=dev) for k, v in
+                dict(normal=normals, point=points, left=lefts, right=rights, value=vals, roots=roots).items()}
 
-    def _predict_raw(self, frame):
-        X, _ = self._dinfo.expand(frame, pad=False)
+    def _pack(self, dev):
+        self._packed = self._dense_pack(self._trees, dev)
+
+    def _sparse_pack(self):
+        """ops.eif_ops pack of the whole forest: derived from _trees on first
+        use, rebuilt when _trees is another list or has grown, never saved
+        (models/state_io.py skips _eif_sparse)."""
+        from ...ops import eif_ops
+        held = getattr(self, "_eif_sparse", None)
+        if held is None or held[0] is not self._trees or held[1] != len(self._trees):
+            held = self._eif_sparse = (self._trees, len(self._trees), eif_ops.pack_hyperplane_forest(self._trees))
+        return held[2]
+
+    def _dense_lengths(self, P, X, tot, t0, t1):
+        """tot += leaf values of trees t0..t1-1 of the dense pack P: every
+        column of every visited node, [n, P] f64 temporaries."""
         X = torch.nan_to_num(X.to(torch.float64))
-        P = self._packed
         n = X.shape[0]
-        tot = torch.zeros(n, dtype=torch.float64, device=X.device)
-        for r in P["roots"].tolist():
+        for r in P["roots"][t0:t1].tolist():
             nd = torch.full((n,), r, dtype=torch.int64, device=X.device)
             for _ in range(self._height + 1):
                 l = P["left"][nd]
@@ -300,9 +334,34 @@ class H2OExtendedIsolationForestEstimator(H2OEstimator):
                 nxt = torch.where(proj <= 0, l, P["right"][nd])
                 nd = torch.where(act, nxt, nd)
             tot += P["value"][nd]
-        ml = tot / len(self._trees)
+
+    def _add_lengths(self, X, tot, t0, t1):
+        """tot[r] += path lengths of trees t0..t1-1 for the rows of X (f32, as
+        expand returns it).  On a GPU the sparse-table kernel (ops/eif_ops.py);
+        on a CPU, or with H2O3_TREE_EIF=torch, the dense rule.  While _fit is
+        growing trees the range is packed on its own."""
+        if t0 >= t1:
+            return
+        fitted = self._packed is not None
+        a, b = (t0, t1) if fitted else (0, t1 - t0)
+        if X.is_cuda and os.environ.get("H2O3_TREE_EIF", "") != "torch":
+            from ...ops import eif_ops
+            pack = self._sparse_pack() if fitted else eif_ops.pack_hyperplane_forest(self._trees[t0:t1])
+            eif_ops.hyperplane_forest_lengths(pack, X.contiguous(), a, b, out=tot)
+        else:
+            self._dense_lengths(self._packed if fitted else self._dense_pack(self._trees[t0:t1], X.device),
+                                X, tot, a, b)
+
+    def _raw_from_total(self, tot, ntrees):
+        ml = tot / ntrees
         score = torch.pow(2.0, -ml / c_factor(self._psi))
         return torch.stack([score, ml], 1)
+
+    def _predict_raw(self, frame):
+        X, _ = self._dinfo.expand(frame, pad=False)
+        tot = torch.zeros(X.shape[0], dtype=torch.float64, device=X.device)
+        self._add_lengths(X, tot, 0, len(self._trees))
+        return self._raw_from_total(tot, len(self._trees))
 
     def predict(self, test_data, **kw):
         raw = self._predict_raw(test_data)
@@ -311,6 +370,10 @@ class H2OExtendedIsolationForestEstimator(H2OEstimator):
                                   ["anomaly_score", "mean_length"])
 
     def _score_unsupervised(self, spec):
-        raw = self._predict_raw(spec.frame)
-        self._training_metrics = mm.ModelMetricsAnomaly(mean_score=float(raw[:, 0].mean()),
-                                                        mean_length=float(raw[:, 1].mean()), nobs=spec.frame.nrows)
+        # with score_tree_interval, _fit has already walked every tree over the training frame
+        means = getattr(self, "_train_means", None)
+        if means is None:
+            raw = self._predict_raw(spec.frame)
+            means = (float(raw[:, 0].mean()), float(raw[:, 1].mean()))
+        self._training_metrics = mm.ModelMetricsAnomaly(mean_score=means[0], mean_length=means[1],
+                                                        nobs=spec.frame.nrows)

@@ -28,7 +28,6 @@ _TABLE = {
     """,
     "dl_shap": """
         h2o_dl_shap_chunk  i
-        h2o_dl_shap_lds    q  iP
         h2o_dl_shap_pairs  i  iPPPPPPPPPPiiPPqqqiiP
     """,
     "fairness": """
@@ -69,6 +68,9 @@ _TABLE = {
     "metrics": """
         h2o_logit_hist    i  PPPqiPPP
         h2o_group_reduce  i  PPqiiiPP
+    """,
+    "tree_eif": """
+        h2o_eif_lengths  i  PqiPPPPiiPPiiP
     """,
     "tree_hist": """
         h2o_hist_quad           i  PiPPPPiiiiffPiiiPiqiiPPP

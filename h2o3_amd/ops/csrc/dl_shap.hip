@@ -312,14 +312,9 @@ static size_t dl_shap_plan(DLShapNet& net, int nl, const int* width) {
   return (size_t)off * sizeof(float);
 }
 
-extern "C" {
-
-// background rows per slice: a launch with B rows writes ceil(B / chunk) slices
-int h2o_dl_shap_chunk() { return DLS_CHUNK; }
-
 // LDS bytes of the plan for width[0 .. nl] (inputs, hidden layers), or -1
 // when the network does not fit (more than 8 hidden layers, > 160 KiB)
-long long h2o_dl_shap_lds(int nl, const int* width) {
+static long long dl_shap_lds(int nl, const int* width) {
   if (nl < 1 || nl > DLS_MAXL) return -1;
   for (int l = 0; l <= nl; ++l)
     if (width[l] < 1 || width[l] > (1 << 20)) return -1;
@@ -327,6 +322,11 @@ long long h2o_dl_shap_lds(int nl, const int* width) {
   const size_t bytes = dl_shap_plan(net, nl, width);
   return bytes <= DLS_LDS_BYTES ? (long long)bytes : -1;
 }
+
+extern "C" {
+
+// background rows per slice: a launch with B rows writes ceil(B / chunk) slices
+int h2o_dl_shap_chunk() { return DLS_CHUNK; }
 
 // Pair stage for N test rows x B background rows.  width[nl + 1], act[nl],
 // scale[nl], W / PX / PZ[nl] per hidden layer (bottom up); S [N, B] or null.
@@ -338,7 +338,7 @@ int h2o_dl_shap_pairs(int nl, const int* width, const int* act, const float* sca
                       const float* out_w, const float* S, int N, int B, float* partial, double* out,
                       long long row_off, long long bg_off, long long Btot, int per_ref, int swap, hipStream_t s) {
   if (N <= 0 || B <= 0) return 0;
-  if (h2o_dl_shap_lds(nl, width) < 0) return -2;
+  if (dl_shap_lds(nl, width) < 0) return -2;
   DLShapNet net{};
   const size_t lds_bytes = dl_shap_plan(net, nl, width);
   net.nl = nl;
