@@ -869,7 +869,15 @@ __global__ __launch_bounds__(256) void hist_bm_reduce_kernel(
       a0 += cnt;
       a1 += (long long)(v & ((1ull << 40) - 1)) - cnt * bq;
     } else {
-      a0 += (long long)v;
+      // one item sums to 2^62 at most (fixed_point_scale), BM_RED items of a
+      // node do not fit int64: the running sum goes to the f64 histogram
+      // before an add that would wrap (never while the sum fits: same bits)
+      long long t;
+      if (__builtin_add_overflow(a0, (long long)v, &t)) {
+        flush();
+        t = (long long)v;
+      }
+      a0 = t;
     }
   }
   flush();
