@@ -155,7 +155,10 @@ class _Fam:
         if f == "negativebinomial":
             th = self.theta
             t1 = torch.where(y > 0, y * torch.log(y.clamp_min(1e-300) / mu), torch.zeros_like(y))
-            t2 = (y + 1 / th) * torch.log((1 + th * y) / (1 + th * mu))
+            # log((1 + th y) / (1 + th mu)) by log1p: at the default th = 1e-10 the
+            # ratio form loses ~1e-16 / th = 1e-6 per row in fp64 (and the whole
+            # term in f32)
+            t2 = (y + 1 / th) * torch.log1p(th * (y - mu) / (1 + th * mu))
             return 2 * (t1 - t2)
         raise ValueError(f)
 

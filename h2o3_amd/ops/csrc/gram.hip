@@ -131,17 +131,26 @@ __device__ __forceinline__ float gi_linkinv(int link, float eta) {
     default: return eta;
   }
 }
-__device__ __forceinline__ float gi_dmu(int link, float mu) {
+// 1 - mu.  Logit link: exp(-eta) mu, which keeps the complement where mu has
+// rounded to 1 (eta > 17: with 1.f - mu == 0 the weight fell to its 1e-10
+// floor and (y - mu) / d of a y = 0 row grew by mu (1 - mu) / 1e-10, up to
+// 400 times).  eta < -88: inf * 0 = NaN, and fmaxf in gi_dmu / gi_var then
+// returns the floor.
+__device__ __forceinline__ float gi_comp(int link, float eta, float mu) {
+  return link == 1 ? __expf(-eta) * mu : 1.f - mu;
+}
+// q: gi_comp of the row
+__device__ __forceinline__ float gi_dmu(int link, float mu, float q) {
   switch (link) {
-    case 1: return fmaxf(mu * (1.f - mu), 1e-10f);
+    case 1: return fmaxf(mu * q, 1e-10f);
     case 2: return fmaxf(mu, 1e-10f);
     case 3: return -(mu * mu);
     default: return 1.f;
   }
 }
-__device__ __forceinline__ float gi_var(const GlmFamArgs& f, float mu) {
+__device__ __forceinline__ float gi_var(const GlmFamArgs& f, float mu, float q) {
   switch (f.var) {
-    case 1: return fmaxf(mu * (1.f - mu), 1e-10f);
+    case 1: return fmaxf(mu * q, 1e-10f);
     case 2: return fmaxf(mu, 1e-10f);
     case 3: return fmaxf(mu * mu, 1e-10f);
     case 4: return powf(fmaxf(mu, 1e-10f), f.tvp);
@@ -173,7 +182,16 @@ __device__ __forceinline__ float gi_dev(const GlmFamArgs& f, float y, float mu) 
     case 5: {
       const float th = f.theta;
       const float t1 = y > 0.f ? y * __logf(y / mu) : 0.f;
-      const float t2 = (y + 1.f / th) * __logf((1.f + th * y) / (1.f + th * mu));
+      // log((1 + th y) / (1 + th mu)) = log1p(u), u = th (y - mu) / (1 + th mu):
+      // at small th (default 1e-10) 1 + th y rounds to 1 in f32 and the 1 / th
+      // factor turns the lost term, about y - mu, into the whole answer.
+      // |u| < 2^-6: four series terms (the fifth is below 2^-26 relative);
+      // beyond, rounding 1 + u costs at most 2^-24 / 2^-6 of the logarithm
+      // (no log1pf call: it spilled registers in the P = 128 bf16x3 kernel)
+      const float u = th * (y - mu) / (1.f + th * mu);
+      const float l1p = fabsf(u) < 0.015625f ? u * (1.f - u * (0.5f - u * (0.33333334f - 0.25f * u)))
+                                             : __logf(1.f + u);
+      const float t2 = (y + 1.f / th) * l1p;
       return 2.f * (t1 - t2);
     }
     default: return (y - mu) * (y - mu);
@@ -372,8 +390,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             W = sw;
             z = sy - so;
           } else {
-            const float d = gi_dmu(fam.link, mu);
-            W = sw * d * d / gi_var(fam, mu);
+            const float q = gi_comp(fam.link, eta, mu);
+            const float d = gi_dmu(fam.link, mu, q);
+            W = sw * d * d / gi_var(fam, mu, q);
             z = (eta - so) + (sy - mu) / d;
           }
           if (sw != 0.f) dev += (double)(sw * gi_dev(fam, sy, mu));
@@ -725,7 +744,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             } else if (fam.link == 1 && fam.var == 1) {
               // canonical binomial: dmu/deta == variance, so W = w d and one
               // reciprocal; 0/1 responses need one log for the deviance
-              const float d = fmaxf(mu * (1.f - mu), 1e-10f);
+              const float d = fmaxf(mu * gi_comp(1, eta, mu), 1e-10f);
               W = sw * d;
               z = (eta - so) + (sy - mu) * __frcp_rn(d);
               rres = sw * (sy - mu);
@@ -736,8 +755,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 dev += (double)(sw * dv);
               }
             } else {
-              const float d = gi_dmu(fam.link, mu);
-              const float wd = sw * d / gi_var(fam, mu);
+              const float q = gi_comp(fam.link, eta, mu);
+              const float d = gi_dmu(fam.link, mu, q);
+              const float wd = sw * d / gi_var(fam, mu, q);
               W = wd * d;
               z = (eta - so) + (sy - mu) / d;
               rres = wd * (sy - mu);
@@ -1197,8 +1217,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RW == 1 ? 4
         z = sy - so;
         rres = sw * (sy - eta);
       } else {
-        const float d = gi_dmu(fam.link, mu);
-        const float wd = sw * d / gi_var(fam, mu);
+        const float q = gi_comp(fam.link, eta, mu);
+        const float d = gi_dmu(fam.link, mu, q);
+        const float wd = sw * d / gi_var(fam, mu, q);
         W = wd * d;
         z = (eta - so) + (sy - mu) / d;
         rres = wd * (sy - mu);

@@ -13,6 +13,7 @@ from . import _native
 from ._native import check as _check, ptr as _ptr, stream as _stream
 
 _pairs_cache = {}
+_pair_index_cache = {}
 
 
 def _lib():
@@ -27,14 +28,28 @@ def _pairs(T, device):
     return _pairs_cache[key]
 
 
+def _pair_index(pairs_t, T):
+    """The int64 (i, j) index vectors of _pairs(T, device)'s tensor, made once
+    (two conversion launches per IRLS pass otherwise)."""
+    key = (T, pairs_t.device)
+    if key not in _pair_index_cache:
+        _pair_index_cache[key] = (pairs_t[:, 0].long(), pairs_t[:, 1].long())
+    return _pair_index_cache[key]
+
+
 def _assemble(tiles, pairs_t, T):
-    """[npairs, t, t] upper-triangle tiles -> symmetric [tT, tT]."""
+    """[npairs, t, t] upper-triangle tiles -> symmetric [tT, tT].  Diagonal
+    tiles are averaged with their transpose: the kernels sum a diagonal
+    tile's (i, j) and (j, i) in different orders (bf16x3: hi lo before lo hi;
+    f32: x_i (w x_j) against x_j (w x_i)), so they differ in the last f32
+    bits; off-diagonal tiles are mirrored and keep their values."""
     t = tiles.shape[-1]
-    ii, jj = pairs_t[:, 0].long(), pairs_t[:, 1].long()
+    ii, jj = _pair_index(pairs_t, T)
     Gb = torch.zeros((T, T, t, t), dtype=torch.float64, device=tiles.device)
     Gb[jj, ii] = tiles.transpose(1, 2)
     Gb[ii, jj] = tiles
-    return Gb.permute(0, 2, 1, 3).reshape(t * T, t * T)
+    G = Gb.permute(0, 2, 1, 3).reshape(t * T, t * T)
+    return (G + G.T).mul_(0.5)
 
 
 _LINK = {"identity": 0, "logit": 1, "log": 2, "inverse": 3}
@@ -55,6 +70,15 @@ def _f32(t):
     return None if t is None else t.to(torch.float32).contiguous()
 
 
+# Fewest rows on the bf16x3 Gram.  One bf16x3 product (hi hi + hi lo + lo hi,
+# lo rounded to bf16, unit roundoff 2^-8) can be off by 3 * 2^-16 = 4.6e-5 of
+# |x_i x_j|; an entry holds the 2e-5 (of sqrt(G_ii G_jj)) the IRLS Hessian is
+# kept to only because the roundings of its rows average out.  With less than
+# one 64-row chunk there is little to average (one row: measured 2.5e-5) and
+# nothing to gain in time, so such passes take the f32 MFMA.
+_BF3_MIN_ROWS = 64
+
+
 def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, codes=(0, 0), tvp=0.0, theta=1e-10,
              W=None, z=None, signed=None, target_blocks=1024, width=None, grad=False, bf3=True, grad_f64=True,
              dbg=0):
@@ -72,8 +96,9 @@ def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, cod
     (exact f64 products of the f32 values, f64 sums -- or, grad_f64=False,
     f32 products summed over a lane's rows of a chunk, f64 beyond; g[Pp] =
     sum r) as a third element.
-    `bf3` (Pp = 128 ws path): True bf16x3 MFMA Gram, False f32 MFMA, "bf16"
-    one bf16 MFMA per product (fused passes with grad=True only).
+    `bf3` (Pp = 128 ws path): True bf16x3 MFMA Gram (from _BF3_MIN_ROWS rows
+    on, f32 MFMA below), False f32 MFMA, "bf16" one bf16 MFMA per product
+    (fused passes with grad=True only).
     `dbg` (microbenchmarks): bit 0 skips the MFMAs, bit 1 the row loads.
     """
     N, ldx = X.shape
@@ -94,6 +119,8 @@ def glm_irls(X, aug=-1, beta=None, b0=0.0, y=None, wprior=None, offset=None, cod
     dev = torch.zeros(splits, dtype=torch.float64, device=X.device)
     gout = torch.empty((splits, P + 1), dtype=torch.float64, device=X.device) if grad else None
     X = X.contiguous()
+    if bf3 and bf3 != "bf16" and N < _BF3_MIN_ROWS:
+        bf3 = False
     bt = _f32(beta)
     keep = [_f32(y), _f32(wprior), _f32(offset), _f32(W), _f32(z)]
     if signed is None:
