@@ -30,7 +30,7 @@ from ...parallel import collectives as coll
 from ..base import ScoreKeeper, ScoreSchedule, _LESS_IS_BETTER
 from ..distributions import get_distribution
 from .engine import GrowParams, TreeGrower
-from ...ops import tree_ops
+from ...ops import quantile_ops, tree_ops
 from ...utils.timer import phase
 from .shared import Forest, SharedTreeEstimator
 from ...core.groupsum import index_add as _ia
@@ -61,6 +61,7 @@ class GbmSwitches:
     pos_leaf: bool = True         # H2O3_POS_LEAF: leaf sums from the position-ordered payload, device values
     gbm_grad: bool = True         # H2O3_GBM_GRAD: the residual kernel writes the grower's root payload
     leaf_scatter: bool = True     # H2O3_LEAF_SCATTER: write-only per-row leaf values, folded in by the next tree
+    leaf_quantile: bool = True    # H2O3_LEAF_QUANTILE: laplace / quantile / huber quantiles by the radix-select kernel
 
     @classmethod
     def from_env(cls, env=None):
@@ -70,7 +71,7 @@ class GbmSwitches:
         return cls(dev_tree=is1("H2O3_DEV_TREE"), dev_tree_graph=is1("H2O3_DEV_TREE_GRAPH"),
                    leaf_gather=not0("H2O3_LEAF_GATHER"), dev_last_level=not0("H2O3_DEV_LAST_LEVEL"),
                    pos_leaf=is1("H2O3_POS_LEAF"), gbm_grad=is1("H2O3_GBM_GRAD"),
-                   leaf_scatter=is1("H2O3_LEAF_SCATTER"))
+                   leaf_scatter=is1("H2O3_LEAF_SCATTER"), leaf_quantile=is1("H2O3_LEAF_QUANTILE"))
 
 
 class GbmRoute(NamedTuple):
@@ -166,6 +167,17 @@ class GBMDriver:
         self._unit_weights = bool((self.base_w == 1).all()) and float(pp.get("sample_rate", 1.0)) >= 1.0 and \
             pp.get("sample_rate_per_class") is None
         self.offset = spec.offset_tensor()
+        self.sw = GbmSwitches.from_env()    # read once: later changes of the environment do not reach this driver
+        self._base_unit = bool(((self.base_w == 0) | (self.base_w == 1)).all())
+        # the quantile families select on the device (ops/quantile_ops.py).  The
+        # fixed-point scale of their weight sums is one number for all ranks (the
+        # ranks add their tables): every input of it is all-reduced, the 0/1 flag
+        # too -- a shard that happens to hold only 0/1 weights must not scale alone
+        self._wq_bits = None
+        if self.dist.family in ("laplace", "quantile", "huber") and dev.type == "cuda" and self.sw.leaf_quantile:
+            wmax = coll.allreduce_scalar(float(self.base_w.max()) if N else 0.0, op="max")
+            unit = coll.allreduce_scalar(float(self._base_unit), op="min") == 1.0
+            self._wq_bits = quantile_ops.weight_scale_bits(wmax, coll.allreduce_scalar(float(N)), unit)
         # init prediction (reference: GBM.init -> initial value by distribution)
         if self.K == 1:
             if spec.nclasses == 2:
@@ -179,8 +191,11 @@ class GBMDriver:
             if self.dist.family == "custom":
                 f0 = self.dist.init_f(yv, self.base_w, self.offset)
             elif self.dist.family in ("laplace", "quantile", "huber"):
-                f0 = _weighted_quantile(yv[self.base_w > 0], self.base_w[self.base_w > 0],
-                                        0.5 if self.dist.family != "quantile" else self.dist.quantile_alpha)
+                q0 = 0.5 if self.dist.family != "quantile" else self.dist.quantile_alpha
+                if self._wq_bits is not None:
+                    f0 = quantile_ops.global_wquantile(yv, None, self.base_w, q0, self._wq_bits)
+                else:
+                    f0 = _weighted_quantile(yv[self.base_w > 0], self.base_w[self.base_w > 0], q0)
             elif self.dist.link == "logit":
                 mu = min(max(mu, 1e-10), 1 - 1e-10)
                 f0 = math.log(mu / (1 - mu))
@@ -237,8 +252,6 @@ class GBMDriver:
         self._dbuf = None               # onepass: the buffer _dpend points at
         self._hv_ring = [None, None]    # onepass / posleaf: pinned slots of the leaf values' host copy
         self._devtree = None            # devtree: the DevTreeGBM, built by the first step
-        self.sw = GbmSwitches.from_env()    # read once: later changes of the environment do not reach this driver
-        self._base_unit = bool(((self.base_w == 0) | (self.base_w == 1)).all())
         from . import devtree
         self.route = gbm_route(self.sw, dev.type, self.K, self.dist.family, self.dist.link, self.mono_on,
                                self.noise_bw, self._base_unit, self.grower.pos_payload_ok(), devtree.supported(self))
@@ -567,6 +580,10 @@ class GBMDriver:
                              self.noise_bw)
 
     def _update_huber_delta(self, y, f, w):
+        if self._wq_bits is not None:
+            self.dist.huber_delta = quantile_ops.global_wquantile(y, f, w, self.dist.huber_alpha, self._wq_bits,
+                                                                  mode=1)
+            return
         r = (y - f).abs()
         m = w > 0
         self.dist.huber_delta = _weighted_quantile(r[m], w[m], self.dist.huber_alpha)
@@ -576,6 +593,31 @@ class GBMDriver:
         (values, the leaves' denominators or None where the rule has none)."""
         idx = nid.long()
         fam = self.dist.family
+        if self._wq_bits is not None:
+            # selection over the grower's leaf segments: no sort, no per-row host copy
+            lids, st, ct = self.grower.last_segs
+            alpha = self.dist.quantile_alpha if fam == "quantile" else 0.5
+            med = quantile_ops.leaf_wquantile(self.grower.ridx, y, f, w, lids, st, ct, L, alpha, self._wq_bits)
+            if fam != "huber":
+                return med.cpu().numpy(), None
+            d = (y - f).to(torch.float64) - med[idx]
+            corr = torch.sign(d) * d.abs().clamp(max=self.dist.huber_delta)
+            # seg_sum2 reads f32 and sums in f64.  A term rounded to one f32 is off by
+            # 2^-24 of itself, which moves leaf values at 1e-8 and, through f, later
+            # trees; so each f64 term goes in as three f32 parts, 24 bits each.  The
+            # parts add up to the term exactly while mid and lo are normal f32
+            # (terms above ~1e-30; smaller ones lose low bits of no weight), and the
+            # sums then differ from f64 index_add by summation order alone.  Cost:
+            # three N-row temporaries and a second seg_sum2 per tree
+            a = w * corr
+            hi = a.to(torch.float32)
+            mid = (a - hi).to(torch.float32)
+            lo = (a - hi - mid).to(torch.float32)
+            s = torch.cat([tree_ops.seg_sum2(self.grower.ridx, hi, mid, lids, st, ct, L),
+                           tree_ops.seg_sum2(self.grower.ridx, lo, w, lids, st, ct, L)], 1)
+            coll.allreduce_(s)
+            num, den = (s[:, 2] + s[:, 1]) + s[:, 0], s[:, 3]
+            return (med + torch.where(den > 0, num / den.clamp_min(1e-300), torch.zeros_like(num))).cpu().numpy(), None
         if fam in ("laplace", "quantile"):
             alpha = 0.5 if fam == "laplace" else self.dist.quantile_alpha
             return _segmented_wquantile(idx, (y - f).to(torch.float64), w.to(torch.float64), L, alpha), None

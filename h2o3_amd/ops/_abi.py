@@ -58,7 +58,6 @@ _TABLE = {
         h2o_xv                             i  PqiPiPiP
         h2o_kmeans_max_k                   i  ii
         h2o_kmeans_part_stride             q  ii
-        h2o_kmeans_set_debug               v  i
         h2o_kmeans_resident_per_cu         i  iiif
         h2o_kmeans_lloyd                   i  PPqiPPiPPPPiifP
         h2o_kmeans_sums_resident_per_cu    i  ii
@@ -74,7 +73,6 @@ _TABLE = {
     """,
     "tree_hist": """
         h2o_hist_quad           i  PiPPPPiiiiffPiiiPiqiiPPP
-        h2o_hist_bm_set_debug   v  i
         h2o_hist_bm             i  PiPPPPiiiiffPiiPiqiiiPPPP
         h2o_iota_i32            i  PqP
         h2o_hist_build          i  PiiPPPPiiiiffPiiiPiPP
@@ -106,7 +104,6 @@ _TABLE = {
         h2o_dt_root_leaf_iota   i  PPqP
         h2o_leaf_scatter_dev    i  PPiPPPP
         h2o_leaf_flag_sums_dev  i  PPPiPPiiPPP
-        h2o_leaf_gather_lds     i  ii
         h2o_leaf_gather_items   i  qi
         h2o_leaf_gather_dev     i  PiiiPPPPqiiPPPPPP
         h2o_dt_colmask          i  iPPPPPiiPP
@@ -125,6 +122,11 @@ _TABLE = {
         h2o_shap_pairs           i  PiPiPPPPiiiPPdPqiiiiP
         h2o_shap_path_lds_bytes  q  i
         h2o_shap_path            i  PiPPPPPiiiPdPqiP
+    """,
+    "tree_quantile": """
+        h2o_lq_keys    i  PPPPPiidPPP
+        h2o_lq_hist    i  PPPiPiPP
+        h2o_lq_select  i  PiiddPPPPP
     """,
     "tree_split": """
         h2o_split_find_b   i  PiiiPPPdddddiPPiP

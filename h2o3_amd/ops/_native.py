@@ -77,15 +77,25 @@ def build_one_hip(fname: str, force: bool = False, verbose: bool = False) -> str
     name = os.path.splitext(fname)[0]
     out = lib_path(name)
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
-    if force or _needs_build(src, out, headers):
+    # a library built with H2O3_HIPCC_EXTRA (a measuring build: -DH2O_KMEANS_DBG=...)
+    # says so in <out>.flags: other flags than it was built with rebuild it, in
+    # both directions, so no measuring build stays in place unnoticed
+    extra = os.environ.get("H2O3_HIPCC_EXTRA", "").split()
+    stamp = out + ".flags"
+    built_with = open(stamp).read().split() if os.path.exists(stamp) else []
+    if force or built_with != extra or _needs_build(src, out, headers):
         os.makedirs(LIBDIR, exist_ok=True)
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
-               "-ffp-contract=fast", *_source_flags(src), *os.environ.get("H2O3_HIPCC_EXTRA", "").split(),
-               "-I", CSRC, "-o", out + ".tmp", src]
+               "-ffp-contract=fast", *_source_flags(src), *extra, "-I", CSRC, "-o", out + ".tmp", src]
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
         os.replace(out + ".tmp", out)
+        if extra:
+            with open(stamp, "w") as f:
+                f.write(" ".join(extra))
+        elif os.path.exists(stamp):
+            os.remove(stamp)
     return out
 
 

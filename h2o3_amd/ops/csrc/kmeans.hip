@@ -811,7 +811,14 @@ static int km_vrg(int k, int P, bool acc, float fx_scale) {
   return vrg;
 }
 
-static int g_km_dbg = 0;   // microbenchmark phase-skip flags (h2o_kmeans_set_debug); 0 in production
+// microbenchmark phase-skip flags of scripts/kmeans_mb.py (1 MFMA, 2 sums, 4 row
+// stats, 8 global loads, 16 LDS staging); results are wrong with any flag set.
+// A build-time constant (H2O3_HIPCC_EXTRA=-DH2O_KMEANS_DBG=<flags> for a
+// measuring build), not launch state; 0 in production.
+#ifndef H2O_KMEANS_DBG
+#define H2O_KMEANS_DBG 0
+#endif
+static const int g_km_dbg = H2O_KMEANS_DBG;
 
 template <int KT, int MAXV, bool ACC>
 static int km_launch2(const float* X, const float* w, long long N, int P, const float* C, const float* cn, int k,
@@ -870,10 +877,6 @@ int h2o_kmeans_max_k(int P, int acc) {
 }
 
 long long h2o_kmeans_part_stride(int k, int P) { return km_part_stride(k, P); }
-
-// Phase-skip flags for scripts/kmeans_mb.py (1 MFMA, 2 sums, 4 row stats,
-// 8 global loads, 16 LDS staging).  Results are wrong with any flag set.
-void h2o_kmeans_set_debug(int flags) { g_km_dbg = flags; }
 
 // Workgroups of the Lloyd kernel resident per CU for (k, P, acc): the
 // persistent grid is sized to exactly fill the chip (no tail of late

@@ -720,9 +720,12 @@ __global__ __launch_bounds__(1024) void hist_bm_kernel(
 
 // microbenchmark phase switches (scripts/hist_bm_mb.py): 1 = no flush, 2 = no
 // LDS atomics, 4 = flush with integer atomics.  Results are wrong with any
-// bit set; 0 in production.
-static int g_bm_dbg = 0;
-extern "C" void h2o_hist_bm_set_debug(int flags) { g_bm_dbg = flags; }
+// bit set; 0 in production.  A build-time constant (H2O3_HIPCC_EXTRA=
+// -DH2O_HIST_BM_DBG=<flags> for a measuring build), not launch state.
+#ifndef H2O_HIST_BM_DBG
+#define H2O_HIST_BM_DBG 0
+#endif
+static const int g_bm_dbg = H2O_HIST_BM_DBG;
 
 // Ragged last group (h2o_hist_bm's `ragged`): 0 = off (default); 1 = 4 codes
 // per lane, slot stride 16; 2 = 4 codes per lane, slot stride = lanes per row;
@@ -2726,7 +2729,7 @@ int h2o_leaf_flag_sums_dev(const float* zp, const int* work, const int* fbase, i
 // nseg = 2 ints.  last != 0: level D was not compacted (slot_wb = the
 // flag-word bases of the level-(D-1) slots, from h2o_dt_items2).
 #define LG_CHK 8192   // positions per work item of the bounds pass
-int h2o_leaf_gather_lds(int R, int scap) { return (R + 2 * scap + 1) * (int)sizeof(int); }
+#define LG_LDS_BYTES(R, scap) (((R) + 2 * (scap) + 1) * (int)sizeof(int))
 int h2o_leaf_gather_items(long long N, int scap) { return (int)(scap + N / LG_CHK + 1); }
 
 int h2o_leaf_gather_dev(const double* rec, int nh, int D, int last, const int* slot_wb, const int* ridx,
@@ -2737,7 +2740,7 @@ int h2o_leaf_gather_dev(const double* rec, int nh, int D, int last, const int* s
       N > (1ll << 31) - (1 << 24))
     return -1;
   if (last != 0 && (slot_wb == nullptr || flags == nullptr)) return -1;
-  const int lds = h2o_leaf_gather_lds(R, scap);
+  const int lds = LG_LDS_BYTES(R, scap);
   if (lds > 160 * 1024 - 256) return -1;
   static int lds_set = 0;
   if (lds > lds_set) {   // first call is outside any capture (devtree runs its first tree eagerly)

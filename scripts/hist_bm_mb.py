@@ -1,6 +1,10 @@
-"""Micro-benchmark of the bin-major histogram kernel by level shape and phase
-(h2o_hist_bm_set_debug: 1 = no flush, 2 = no LDS atomics, 3 = loads only),
-for every lane mapping of the ragged last group (RAGGED=0,1,2,3: H2O3_HIST_BM_RAGGED)."""
+"""Micro-benchmark of the bin-major histogram kernel by level shape, with the
+partial-table reduction and with the atomic flush, for every lane mapping of
+the ragged last group (RAGGED=0,1,2,3: H2O3_HIST_BM_RAGGED).  The phase
+switches are a build-time constant of tree_hist.hip: build with
+H2O3_HIPCC_EXTRA=-DH2O_HIST_BM_DBG=<1 no flush | 2 no LDS atomics | 3 loads
+only> and run this again for a phase's time (the `full` column then); the next
+build without the variable puts the production library back."""
 import os
 import sys
 import time
@@ -47,9 +51,8 @@ for N in (12_500_000, 100_000_000):
             os.environ["H2O3_HIST_TB"] = tb
         name = f"{name} TB={tb} ragged={rag}"
         line = []
-        for flag in (0, 1, 2, 3, 5):
-            os.environ["H2O3_HIST_BM_RED"] = "0" if flag == 5 else "1"
-            lib.h2o_hist_bm_set_debug(0 if flag == 5 else flag)
+        for red in ("1", "0"):
+            os.environ["H2O3_HIST_BM_RED"] = red
             tree_ops.hist_build(bd, ridx, va, None, 0, starts, counts, len(starts), vmax=vmax, unit_w=True, posv=True)
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -58,8 +61,6 @@ for N in (12_500_000, 100_000_000):
                                     posv=True)
             torch.cuda.synchronize()
             line.append((time.perf_counter() - t) / 5 * 1e3)
-        lib.h2o_hist_bm_set_debug(0)
-        print(f"N={N/1e6:g}M {name:54s} full {line[0]:7.3f}  no-flush {line[1]:7.3f}  no-atomics {line[2]:7.3f}  "
-              f"loads-only {line[3]:7.3f}  atomic-flush {line[4]:7.3f} ms", flush=True)
+        print(f"N={N/1e6:g}M {name:54s} full {line[0]:7.3f}  atomic-flush {line[1]:7.3f} ms", flush=True)
     del bd, va, shapes
     torch.cuda.empty_cache()
