@@ -12,6 +12,7 @@ evaluation.
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -22,7 +23,22 @@ from ...core.groupsum import group_sum
 from ...ops import linalg_ops
 
 
+def _kernel_route(X, K):
+    """The fused HIP pass (linalg_ops.glm_multinomial_pass) serves this fit:
+    a device frame, a shape the kernel holds in LDS, and H2O3_GLM_MULTI not
+    set to `torch`.  Asked once per fit."""
+    return (X.is_cuda and X.dtype == torch.float32 and linalg_ops.glm_multinomial_supported(X.shape[1], K)
+            and os.environ.get("H2O3_GLM_MULTI", "").lower() != "torch")
+
+
 def _loss_grad_multinomial(X, Y, w, B, b0, wsum):
+    """Y: the f64 one-hot response [N, K] with f64 weights (torch route), or,
+    on the kernel route, the int32 class codes [N] with f32 weights."""
+    if Y.dim() == 1:
+        ll, gB, gb = linalg_ops.glm_multinomial_pass(X, Y, w, B, b0, B.shape[1])
+        s = torch.cat([ll.view(1), gB.reshape(-1), gb])
+        coll.allreduce_(s)
+        return float(s[0]) / wsum, s[1:1 + B.numel()].view_as(B) / wsum, s[1 + B.numel():] / wsum
     eta = X @ B.to(X.dtype) + b0.to(X.dtype)
     eta = eta.to(torch.float64)
     lse = torch.logsumexp(eta, 1)
@@ -179,19 +195,31 @@ def fit_multinomial(est, spec, fam):
         valid = (Xv, yv, (okv & (yv >= 0)).to(torch.float64))
     path = []
     if fam == "multinomial":
-        Y = torch.nn.functional.one_hot(y.clamp(min=0), K).to(torch.float64)
+        kern = _kernel_route(X, K)
         B = torch.zeros((Pp, K), dtype=torch.float64, device=dev)
-        cnt = (Y * w.view(-1, 1)).sum(0)
+        if kern:
+            # class codes and f32 weights, once per fit: no [N, K] one-hot
+            Y, wk = y.to(torch.int32), w.to(torch.float32)
+            codes = {id(y): (Y, wk)}
+            cnt = group_sum(y.clamp(min=0), w, K)
+        else:
+            Y, wk = torch.nn.functional.one_hot(y.clamp(min=0), K).to(torch.float64), w
+            cnt = (Y * w.view(-1, 1)).sum(0)
         coll.allreduce_(cnt)
         pri = (cnt / cnt.sum()).clamp_min(1e-10)
         b0 = torch.log(pri) - torch.log(pri).mean()
-        _, gB, _ = _loss_grad_multinomial(X, Y, w, B, b0, wsum)
+        _, gB, _ = _loss_grad_multinomial(X, Y, wk, B, b0, wsum)
         lmax = float(gB.abs().max()) / max(alpha, 1e-2)
         params = torch.cat([B.reshape(-1), b0]).clone()
-        null_dev = 2 * _loss_grad_multinomial(X, Y, w, B, b0, wsum)[0] * wsum
+        null_dev = 2 * _loss_grad_multinomial(X, Y, wk, B, b0, wsum)[0] * wsum
 
         def dev_of(th, Xm, ym, wm, wsm):
-            Ym = torch.nn.functional.one_hot(ym.clamp(min=0), K).to(torch.float64)
+            if kern:
+                if id(ym) not in codes:     # the validation frame, converted once
+                    codes[id(ym)] = (ym.to(torch.int32), wm.to(torch.float32))
+                Ym, wm = codes[id(ym)]
+            else:
+                Ym = torch.nn.functional.one_hot(ym.clamp(min=0), K).to(torch.float64)
             return 2 * _loss_grad_multinomial(Xm, Ym, wm, th[: Pp * K].view(Pp, K), th[Pp * K:], wsm)[0] * wsm
 
         for lam in _lambda_path(est, p, lmax, alpha, wsum, dinfo.P):
@@ -200,7 +228,7 @@ def fit_multinomial(est, spec, fam):
             def f_g(th, l2=l2):
                 Bm = th[: Pp * K].view(Pp, K)
                 bb = th[Pp * K:]
-                f, gB, gb = _loss_grad_multinomial(X, Y, w, Bm, bb, wsum)
+                f, gB, gb = _loss_grad_multinomial(X, Y, wk, Bm, bb, wsum)
                 f += 0.5 * l2 * float((Bm ** 2).sum())
                 gB = gB + l2 * Bm
                 return f, torch.cat([gB.reshape(-1), gb])

@@ -45,11 +45,13 @@ _TABLE = {
         h2o_gram_split           i  PiiiPPqPP
         h2o_glm_wide_split_grid  i  i
         h2o_glm_wide_split       i  PiiiqPfPPPiiffPPiPPP
-        h2o_glm_wide_gram        i  PiiqPiiPiP
-        h2o_glm_wide_gram256     i  PiiqPiiPiiP
+        h2o_glm_wide_gram        i  PiiqPiiPiiiP
         h2o_gram_f64             i  PiiqPPiiqPP
         h2o_xv_f64               i  PiiqPdPP
         h2o_xtr_f64              i  PiiqPiqPP
+    """,
+    "glm_multi": """
+        h2o_glm_multinomial  i  PqiiPPPPiiiqPP
     """,
     "kmeans": """
         h2o_kmeans_assign_resident_per_cu  i  ii

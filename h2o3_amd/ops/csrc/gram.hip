@@ -1503,8 +1503,8 @@ __global__ __launch_bounds__(256, 2) void glm_wide_gram_kernel(const float* __re
 // tile grid) for slice L / npairs.  NB = ceil((P + 1) / 128).
 // dbg bit 0 (timing only): the X descriptor gets zero records, so every X
 // load is dropped by the range check while the instruction stream stays.
-extern "C" int h2o_glm_wide_gram(const float* X, int ldx, int P, long long N, const float* Wr, int S, int fold,
-                                 double* part, int dbg, hipStream_t s) {
+static int wide_gram128(const float* X, int ldx, int P, long long N, const float* Wr, int S, int fold, double* part,
+                        int dbg, hipStream_t s) {
   if (N <= 0) return 0;
   if (ldx < P || S <= 0 || fold <= 0) return -1;
   const int NB = (P + 1 + WG_T - 1) / WG_T;
@@ -1726,8 +1726,8 @@ __global__ __launch_bounds__(512, 1) void glm_wide_gram256_kernel(const float* _
 // bf3 = 0: one bf16 MFMA per product (hi * hi, ~2^-9 relative): the
 // Hessian of a well-conditioned system, whose Newton step on the exact
 // gradient still converges to the exact-gradient fixed point
-extern "C" int h2o_glm_wide_gram256(const float* X, int ldx, int P, long long N, const float* Wr, int S, int fold,
-                                    double* part, int dbg, int bf3, hipStream_t s) {
+static int wide_gram256(const float* X, int ldx, int P, long long N, const float* Wr, int S, int fold, double* part,
+                        int dbg, int bf3, hipStream_t s) {
   if (N <= 0) return 0;
   if (ldx < P || S <= 0 || fold <= 0) return -1;
   const int NB = (P + 1 + WG2_T - 1) / WG2_T;
@@ -1749,6 +1749,15 @@ extern "C" int h2o_glm_wide_gram256(const float* X, int ldx, int P, long long N,
     hipLaunchKernelGGL((glm_wide_gram256_kernel<false, 64>), dim3(npairs * S), dim3(512), lds, s, X, ldx, P, N, Wr,
                        NB, npairs, S, fold, part, dbg);
   return (int)hipGetLastError();
+}
+
+// The one export of the two wide Gram kernels: tile = 128
+// (glm_wide_gram_kernel, bf3 ignored) or 256 (glm_wide_gram256_kernel).
+extern "C" int h2o_glm_wide_gram(const float* X, int ldx, int P, long long N, const float* Wr, int S, int fold,
+                                 double* part, int tile, int dbg, int bf3, hipStream_t s) {
+  if (tile == WG_T) return wide_gram128(X, ldx, P, N, Wr, S, fold, part, dbg, s);
+  if (tile == WG2_T) return wide_gram256(X, ldx, P, N, Wr, S, fold, part, dbg, bf3, s);
+  return -1;
 }
 
 // ---------------------------------------------------------------------------

@@ -297,6 +297,56 @@ def xtr_f64(X: torch.Tensor, P: int, r: torch.Tensor) -> torch.Tensor:
     return part.sum(0)
 
 
+def glm_multinomial_supported(width, K):
+    """True when glm_multinomial_pass runs at this padded width and class
+    count (ops/csrc/glm_multi.hip: B, a 64-row chunk of X and its residuals
+    stay in LDS; wider designs need a column-panelled variant)."""
+    width, K = int(width), int(K)
+    return 32 <= width <= 256 and width % 32 == 0 and 3 <= K <= 64
+
+
+def glm_multinomial_pass(X, y, w, B, b0, K, width=None, slabs=None):
+    """One fused pass of the multinomial kernel (ops/csrc/glm_multi.hip
+    glm_multinomial_kernel) over the rows of X [N, ldx] f32: per row
+    eta = x B + b0, p = softmax(eta), r = w (p - onehot(y)).
+    Returns (loss = sum w (logsumexp(eta) - eta_y) as an f64 scalar tensor,
+    gB [Pp, K] f64 = X'R, gb [K] f64 = sum R): unnormalised local sums on the
+    device.  y: int32 class codes (a code outside 0..K-1 or w == 0 drops the
+    row), w: f32 or None (all ones), B [Pp, K] / b0 [K]: parameters, rounded
+    to f32 here.  `width`: padded width Pp when X is stored wider.
+    `slabs`: number of row slabs (default: about 2048 workgroups of at least
+    64 rows); their f64 records are summed in a fixed order."""
+    N, ldx = X.shape
+    Pp = int(width) if width else ldx
+    K = int(K)
+    if not glm_multinomial_supported(Pp, K):
+        raise ValueError(f"glm_multinomial_pass: width {Pp}, K {K} outside the kernel's range")
+    if X.dtype != torch.float32 or X.stride(1) != 1 or X.stride(0) % 4 or X.data_ptr() % 16:
+        raise ValueError("glm_multinomial_pass: X must be f32, unit column stride, 16-byte aligned rows")
+    if y.dtype != torch.int32 or y.numel() != N or (w is not None and (w.dtype != torch.float32 or w.numel() != N)):
+        raise ValueError("glm_multinomial_pass: y must be int32 [N], w f32 [N] or None")
+    Kp = 16 if K <= 16 else (32 if K <= 32 else 64)
+    Bp = torch.zeros((Pp, Kp), dtype=torch.float32, device=X.device)
+    Bp[:B.shape[0], :K] = B
+    bp = torch.zeros(Kp, dtype=torch.float32, device=X.device)
+    bp[:K] = b0
+    S = int(slabs) if slabs else max(1, min(2048, N // 64))
+    rps = -(-(-(-N // S)) // 64) * 64
+    S = max(1, -(-N // rps))
+    rec = Pp * Kp + Kp + 1
+    if N == 0:
+        part = torch.zeros((1, rec), dtype=torch.float64, device=X.device)
+    else:
+        part = torch.empty((S, rec), dtype=torch.float64, device=X.device)
+        yc = y.contiguous()
+        wc = None if w is None else w.contiguous()
+        _check(_native.get_lib("glm_multi").h2o_glm_multinomial(
+            _ptr(X), N, Pp, X.stride(0), _ptr(yc), _ptr(wc), _ptr(Bp), _ptr(bp), K, Kp, S, rps, _ptr(part),
+            _stream()), "h2o_glm_multinomial")
+    tot = part.sum(0)
+    return tot[rec - 1], tot[:Pp * Kp].view(Pp, Kp)[:, :K], tot[Pp * Kp:Pp * Kp + K]
+
+
 # Row chunks per batched Gram GEMM (`group`): C_b = hi_b^T [hi_b | lo_b] for g
 # chunks of 512K rows in ONE strided-batched bf16 GEMM (f32 out, each chunk's
 # f32 accumulation stays 512K rows long; chunks summed in f64).  One GEMM per
@@ -472,11 +522,7 @@ def wide_gram(X, P, wr, stream=None, bf3=True, tile=256, slices=0):
         part = torch.zeros((npairs * S, T, T), dtype=torch.float64, device=X.device)
     stream = stream or _stream()
     with phase("glm.wide_gram.kernel"):
-        if T == 256:
-            rc = lib.h2o_glm_wide_gram256(_ptr(X), ldx, P, N, _ptr(wr), S, fold, _ptr(part), 0, int(bool(bf3)),
-                                          stream)
-        else:
-            rc = lib.h2o_glm_wide_gram(_ptr(X), ldx, P, N, _ptr(wr), S, fold, _ptr(part), 0, stream)
+        rc = lib.h2o_glm_wide_gram(_ptr(X), ldx, P, N, _ptr(wr), S, fold, _ptr(part), T, 0, int(bool(bf3)), stream)
     _check(rc, "h2o_glm_wide_gram")
     with phase("glm.wide_gram.assemble"):
         return _wide_gram_assemble(part, S, NB, P, T)

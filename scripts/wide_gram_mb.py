@@ -27,8 +27,8 @@ for T, S, dbg, bf3 in arms:
     npairs = NB * (NB + 1) // 2
     part = torch.zeros((npairs * S, T, T), dtype=torch.float64, device="cuda")
     args = [ctypes.c_void_p(X.data_ptr()), P, P, N, ctypes.c_void_p(w.data_ptr()), S, 1024,
-            ctypes.c_void_p(part.data_ptr()), dbg] + ([bf3] if T == 256 else []) + [stream]
-    fn = lib.h2o_glm_wide_gram256 if T == 256 else lib.h2o_glm_wide_gram
+            ctypes.c_void_p(part.data_ptr()), T, dbg, bf3, stream]
+    fn = lib.h2o_glm_wide_gram
     f = lambda: fn(*args)  # noqa: E731
     assert f() == 0
     torch.cuda.synchronize()
