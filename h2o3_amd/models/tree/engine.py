@@ -303,7 +303,7 @@ class TreeGrower:
         # lazy caches
         self._elig_dev, self._ok_cache = {}, {}
         self._ics_cache = self._qmask = self._is_cat_cpu = self._mono_f32 = self._nbins_t = None
-        self._fcat_u8 = self._pw_t = self._cutmat = self._mask_stage = None
+        self._fcat_u8 = self._pw_t = self._cutmat = self._mask_stage = self._uplift_cat = None
         self._d2h_ring, self._d2h_ev, self._d2h_k = [None, None], [None, None], 0
 
     # ------------------------------------------------------------------ hist
@@ -706,6 +706,9 @@ class TreeGrower:
         """Dispatch: fused HIP kernel for numeric features on GPU (categorical
         features, which need a per-node sort of bins, go through the torch path)."""
         H = self._adapt_hist(H)
+        if self.p.criterion.startswith("uplift") and self.dev.type == "cuda" and H.shape[0] > 0 and \
+                tree_ops.uplift_fits(H.shape[2]) and tree_ops.env("H2O3_UPLIFT_SPLIT", "hip") != "torch":
+            return self._find_splits_uplift(H, col_mask)
         if self.dev.type != "cuda" or self.p.criterion.startswith("uplift"):
             Fl_ = H.shape[0]
             cmf = col_mask[:, self.f0:self.f0 + Fl_]
@@ -747,6 +750,26 @@ class TreeGrower:
                 res[k] = torch.where(b, rc[k].to(res[k].dtype), res[k])
         if self.W > 1:
             res = self._merge_candidates(res, H.shape[1], H.shape[2], H.shape[3])
+        return res
+
+    def _find_splits_uplift(self, H, col_mask):
+        """Uplift divergence split search on the kernels of tree_uplift.hip
+        (one wave per (node, feature) pair, one selection per node): the whole
+        frontier in two launches, no node chunking."""
+        Fl, n, Bs, C = H.shape
+        fsl = slice(self.f0, self.f0 + Fl)
+        if getattr(col_mask, "_all_true", False):
+            ok = self._ok_cache.get(n)
+            if ok is None:
+                ok = self._ok_cache[n] = torch.ones((n, Fl), dtype=torch.uint8, device=self.dev)
+        else:
+            ok = col_mask[:, fsl].to(torch.uint8).contiguous()
+            ok = tree_ops._h2d(ok.numpy(), self.dev) if ok.device.type == "cpu" else ok
+        if self._uplift_cat is None:
+            self._uplift_cat = self.is_cat_t[fsl].to(torch.uint8).contiguous()
+        res = tree_ops.uplift_splits(H, ok, self._uplift_cat, self.f0, self.bd.F, self.p.criterion, self.p.min_rows)
+        if self.W > 1:
+            res = self._merge_candidates(res, n, Bs, C)
         return res
 
     def _find_splits_native(self, H, col_mask, node_wyy, want_pk=False):

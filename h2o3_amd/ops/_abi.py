@@ -54,9 +54,8 @@ _TABLE = {
         h2o_glm_multinomial  i  PqiiPPPPiiiqPP
     """,
     "kmeans": """
-        h2o_kmeans_assign_resident_per_cu  i  ii
+        h2o_kmeans_assign_resident_per_cu  i  iii
         h2o_kmeans_assign                  i  PqiPPiPPiP
-        h2o_xv_resident_per_cu             i  ii
         h2o_xv                             i  PqiPiPiP
         h2o_kmeans_max_k                   i  ii
         h2o_kmeans_part_stride             q  ii
@@ -111,8 +110,7 @@ _TABLE = {
         h2o_dt_colmask          i  iPPPPPiiPP
     """,
     "tree_pd": """
-        h2o_pd_block_threads  i  ii
-        h2o_pd_lds_bytes      q  iii
+        h2o_pd_launch_shape   q  iiP
         h2o_forest_pd_chunk   i  PqiPiPPPPPPiiPiPiiiiPiPqiP
     """,
     "tree_predict": """
@@ -129,6 +127,10 @@ _TABLE = {
         h2o_lq_keys    i  PPPPPiidPPP
         h2o_lq_hist    i  PPPiPiPP
         h2o_lq_select  i  PiiddPPPPP
+    """,
+    "tree_uplift": """
+        h2o_uplift_pairs   i  PiiiPPiidiPP
+        h2o_uplift_select  i  PPiiiPiPPPPP
     """,
     "tree_split": """
         h2o_split_find_b   i  PiiiPPPdddddiPPiP

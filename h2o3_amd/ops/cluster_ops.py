@@ -149,7 +149,7 @@ def _lloyd_split(lib, X, C32, cn, wt, k, P, ntiles, assign, dmin, xabs_max, stri
     d2 = dmin if (dmin is not None and dmin.dtype == torch.float32 and dmin.is_contiguous()) else \
         torch.empty(N, dtype=torch.float32, device=dev)
     import os
-    per_cu = int(lib.h2o_kmeans_assign_resident_per_cu(k, P))
+    per_cu = int(lib.h2o_kmeans_assign_resident_per_cu(k, P, 0))
     if per_cu > 0 and os.environ.get("H2O3_KM_ASSIGN", "wave") == "wave":
         # wave-persistent assignment kernel: X rows in registers, only the
         # centers in LDS (kmeans_assign_kernel)
@@ -230,7 +230,7 @@ def xv(X, V, min_rows=None):
     Xc = X.contiguous()
     Vt = V.to(device=X.device, dtype=torch.float32).t().contiguous()      # [k, W]
     out = torch.empty((N, k), dtype=torch.float32, device=X.device)
-    per_cu = int(lib.h2o_xv_resident_per_cu(k, W))
+    per_cu = int(lib.h2o_kmeans_assign_resident_per_cu(k, W, 1))
     if per_cu < 1:
         return X.to(torch.float64) @ V.to(device=X.device, dtype=torch.float64)
     G = max(1, min(-(-N // 64), per_cu * _cu_count(X.device)))

@@ -634,10 +634,13 @@ static int ka_dispatch(const float* X, long long N, int P, const float* C, const
   return ka_launch<16, MODE>(X, N, P, C, cn, k, assign, d2, G, s, per_cu_out);
 }
 
-extern "C" int h2o_kmeans_assign_resident_per_cu(int k, int P) {
+// Resident workgroups per CU of the wave kernel: mode 0 the assignment pass
+// (h2o_kmeans_assign), mode 1 the projection (h2o_xv); 0 = shape not served.
+extern "C" int h2o_kmeans_assign_resident_per_cu(int k, int P, int mode) {
   int pc = 0;
-  if (ka_dispatch(nullptr, 0, P, nullptr, nullptr, k, nullptr, nullptr, 0, nullptr, &pc) != 0) return 0;
-  return pc;
+  const int rc = mode == 1 ? ka_dispatch<1>(nullptr, 0, P, nullptr, nullptr, k, nullptr, nullptr, 0, nullptr, &pc)
+                           : ka_dispatch<0>(nullptr, 0, P, nullptr, nullptr, k, nullptr, nullptr, 0, nullptr, &pc);
+  return rc != 0 ? 0 : pc;
 }
 
 // Assignment pass of the split path: assign[N] (int32) and d2[N] (f32,
@@ -651,13 +654,7 @@ extern "C" int h2o_kmeans_assign(const float* X, long long N, int P, const float
 
 // out [N][k] f32 = X [N][P] . V^T with V given as [k][P] rows (k <= 256,
 // P % 4 == 0): the projections of PCA / SVD (X v_j) on the f32 matrix cores,
-// X read once.  G workgroups of 4 waves (h2o_xv_resident_per_cu per CU).
-extern "C" int h2o_xv_resident_per_cu(int k, int P) {
-  int pc = 0;
-  if (ka_dispatch<1>(nullptr, 0, P, nullptr, nullptr, k, nullptr, nullptr, 0, nullptr, &pc) != 0) return 0;
-  return pc;
-}
-
+// X read once.  G workgroups of 4 waves (h2o_kmeans_assign_resident_per_cu, mode 1, per CU).
 extern "C" int h2o_xv(const float* X, long long N, int P, const float* V, int k, float* out, int G, hipStream_t s) {
   if (N <= 0) return 0;
   if (G <= 0 || !out) return (int)hipErrorInvalidValue;

@@ -142,15 +142,19 @@ __global__ __launch_bounds__(256) void pd_walk_kernel(
 
 // Threads per block for gc grid points and a stack of `depth` entries: 256,
 // halved until the block's LDS fits the 160 KiB of a CU; 0 when 64 do not fit.
-extern "C" int h2o_pd_block_threads(int gc, int depth) {
+static int pd_block_threads(int gc, int depth) {
   if (depth < 1) depth = 1;
   int th = 256;
   while (th >= 64 && pd_lds_bytes(th, gc, depth) > 160 * 1024) th >>= 1;
   return th >= 64 ? th : 0;
 }
 
-extern "C" long long h2o_pd_lds_bytes(int threads, int gc, int depth) {
-  return (long long)pd_lds_bytes(threads, gc, depth < 1 ? 1 : depth);
+// Threads per block (into *threads, host memory; 0 = shape not served) and the
+// LDS bytes per block (returned) of a launch for gc grid points at that depth.
+extern "C" long long h2o_pd_launch_shape(int gc, int depth, int* threads) {
+  const int th = pd_block_threads(gc, depth);
+  if (threads) *threads = th;
+  return (long long)pd_lds_bytes(th, gc, depth < 1 ? 1 : depth);
 }
 
 // One chunk of gc <= 64 grid points (grid columns [g0, g0 + gc) of grid [S, G])
@@ -171,7 +175,7 @@ extern "C" int h2o_forest_pd_chunk(const float* X, long long ldx, int R, const i
   for (int i = 0; i < PD_MAX_COLS; ++i) pc.c[i] = i < S ? cols[i] : -1;
   int sd = depth < gc - 1 ? depth : gc - 1;   // stack bound
   if (sd < 1) sd = 1;
-  const int threads = h2o_pd_block_threads(gc, sd);
+  const int threads = pd_block_threads(gc, sd);
   if (threads == 0) return (int)hipErrorInvalidValue;
   const size_t lds = pd_lds_bytes(threads, gc, sd);
   if (lds > 64 * 1024) {

@@ -78,8 +78,9 @@ def launch_shape(G, depth):
     of G <= 64 grid points on a forest of that depth."""
     lib = _native.get_lib("tree_pd", required=True)
     sd = max(1, min(int(depth), int(G) - 1))
-    th = lib.h2o_pd_block_threads(int(G), sd)
-    return th, int(lib.h2o_pd_lds_bytes(th, int(G), sd))
+    th = ctypes.c_int(0)
+    lds = lib.h2o_pd_launch_shape(int(G), sd, ctypes.byref(th))
+    return th.value, int(lds)
 
 
 def forest_grid_sums(P, X, K, cols, grid, row0=0, nrows=None) -> GridResult:

@@ -1066,3 +1066,46 @@ def seg_sum2(ridx, a, b, leaf_ids, starts, counts, n_leaves, use_native=None, ch
         if b is not None:
             out[lid, 1] = b[r].to(torch.float64).sum()
     return out
+
+
+# ---------------------------------------------------------------- uplift split search
+UPLIFT_CRITERIA = {"uplift_kl": 0, "uplift_chisquared": 1, "uplift_euclidean": 2}
+_UPLIFT_MAX_BINS = 1024      # value bins one pair stages in LDS (tree_uplift.hip)
+
+
+def uplift_fits(Bs) -> bool:
+    """Whether a histogram of Bs bins (the last one NA) fits the LDS staging
+    of the uplift split kernels."""
+    return 1 <= int(Bs) - 1 <= _UPLIFT_MAX_BINS
+
+
+def uplift_splits(H, col_mask_local, is_cat_local, f0, F, criterion, min_rows):
+    """Best uplift split of every node from the level histogram H [Fl, n, Bs, 4]
+    (f64 on the GPU; channels wt, wt*y, wc, wc*y; bin Bs-1 = NA) on the kernels
+    of tree_uplift.hip: one record per (node, feature) pair, then one
+    selection per node.  col_mask_local [n, Fl]: eligible pairs; is_cat_local
+    [Fl]; f0: global id of local feature 0; features >= F are padding.
+    Returns the dict of TreeGrower._find_splits_torch_core."""
+    lib = _native.get_lib("tree_uplift", required=True)
+    Fl, n, Bs, C = H.shape
+    if C != 4 or not H.is_cuda or not uplift_fits(Bs) or Fl < 1 or n < 1:
+        raise ValueError(f"uplift_splits: histogram {tuple(H.shape)} on {H.device} is not served")
+    dev = H.device
+    H = H.to(torch.float64).contiguous()
+    ok = col_mask_local.to(device=dev, dtype=torch.uint8).contiguous()
+    cat = is_cat_local.to(device=dev, dtype=torch.uint8).contiguous()
+    if tuple(ok.shape) != (n, Fl) or cat.numel() != Fl:
+        raise ValueError("uplift_splits: mask shapes do not match the histogram")
+    rec = torch.empty((n, Fl, 10), dtype=torch.float64, device=dev)
+    fout = torch.empty(13 * n, dtype=torch.float64, device=dev)
+    iout = torch.empty((3, n), dtype=torch.int64, device=dev)
+    na_left = torch.empty(n, dtype=torch.uint8, device=dev)
+    mask = torch.empty((n, Bs), dtype=torch.uint8, device=dev)
+    s = _stream()
+    _check(lib.h2o_uplift_pairs(_ptr(H), Fl, n, Bs, _ptr(ok), _ptr(cat), int(f0), int(F), float(min_rows),
+                                UPLIFT_CRITERIA[criterion], _ptr(rec), s), "h2o_uplift_pairs")
+    _check(lib.h2o_uplift_select(_ptr(rec), _ptr(H), Fl, n, Bs, _ptr(cat), int(f0), _ptr(fout), _ptr(iout),
+                                 _ptr(na_left), _ptr(mask), s), "h2o_uplift_select")
+    return {"gain": fout[:n], "feat": iout[0], "t": iout[1], "opt": iout[2], "na_left": na_left.view(torch.bool),
+            "mask": mask, "L": fout[n:5 * n].view(n, 4), "R": fout[5 * n:9 * n].view(n, 4),
+            "tot": fout[9 * n:].view(n, 4)}
