@@ -10,15 +10,17 @@ NONE / AVERAGE, pre_trained vectors import).
 
 MI355X design: the reference trains word-by-word Hogwild threads; here
 every epoch's (center, context) pairs are generated on the device at
-once and trained in large mini-batches: one gather of the centre vectors,
-one gather of all Huffman path nodes [B, L, d], a batched dot, and
-scatter-add (index_add_) updates of both embedding tables -- the same
-update rule applied to thousands of pairs per kernel instead of one.
+once and trained in large mini-batches -- the same update rule applied to
+thousands of pairs per launch instead of one.  The rule is ops/w2v_ops.py:
+on a GPU three HIP kernels per batch (csrc/w2v.hip: one wave per example,
+the hot Huffman nodes accumulated in LDS), on the CPU or for vec_size > 512
+torch gathers and index_add_; `_output["w2v_route"]` says which ran.
 """
 from __future__ import annotations
 
 import heapq
 import math
+import time
 
 import numpy as np
 import pandas as pd
@@ -26,10 +28,9 @@ import torch
 
 from ..core.frame import H2OFrame
 from ..core.vec import T_REAL, T_STR, Vec, make_enum_from_strings
+from ..ops import w2v_ops
 from ..parallel import cloud
 from .base import H2OEstimator
-
-_MAX_EXP = 6.0      # WordVectorTrainer.MAX_EXP
 
 W2V_DEFAULTS = dict(vec_size=100, window_size=5, sent_sample_rate=1e-3, norm_model="HSM", epochs=5,
                     min_word_freq=5, init_learning_rate=0.025, word_model="SkipGram", pre_trained=None, seed=-1)
@@ -114,14 +115,7 @@ class H2OWord2vecEstimator(H2OEstimator):
         syn0 = ((torch.rand((V, d), generator=g) - 0.5) / d).to(dev)
         syn1 = torch.zeros((max(V - 1, 1), d), device=dev)
         codes, points = _huffman(counts)
-        L = max(1, max(len(c) for c in codes))
-        code_t = torch.full((V, L), -1, dtype=torch.float32)
-        pt_t = torch.zeros((V, L), dtype=torch.long)
-        for i in range(V):
-            n = len(codes[i])
-            code_t[i, :n] = torch.tensor(codes[i], dtype=torch.float32)
-            pt_t[i, :n] = torch.tensor(points[i], dtype=torch.long)
-        code_t, pt_t = code_t.to(dev), pt_t.to(dev)
+        tb = w2v_ops.HuffmanTables(codes, points, dev)
         # token stream (-1 = sentence break / OOV dropped like the reference)
         ids = np.array([self._index.get(w, -2) if w is not None else -1 for w in words], dtype=np.int64)
         ids = ids[ids != -2]
@@ -144,6 +138,12 @@ class H2OWord2vecEstimator(H2OEstimator):
         if str(p.get("norm_model") or "HSM").lower() != "hsm":
             raise ValueError("norm_model: only HSM (hierarchical softmax) is available (Word2Vec.NormModel)")
         cbow = wm == "cbow"
+        # the per-batch update rule (ops/w2v_ops.py): the HIP kernels on a GPU,
+        # the torch rule on the CPU; the kernel route's temporaries are made once
+        self._output["w2v_route"] = w2v_ops.route(syn0)
+        scratch = w2v_ops.Scratch(B, d, tb, dev) if self._output["w2v_route"] == "hip" else None
+        step = w2v_ops.hsm_step
+        t_loop = time.perf_counter()
         for ep in range(epochs):
             # frequent-word sub-sampling (word2vec formula)
             if ss > 0:
@@ -171,23 +171,7 @@ class H2OWord2vecEstimator(H2OEstimator):
                     lr = max(lr0 * (1 - prog), lr0 * 1e-4)
                     idx = order[s:s + B]
                     m = okm[idx]
-                    bag = m.sum(1)
-                    ctxw = t_e[Jc[idx]]                                  # [b, 2w]
-                    h = (syn0[ctxw] * m.unsqueeze(2)).sum(1) / bag.clamp_min(1).unsqueeze(1)
-                    c = t_e[idx]
-                    pts, cds = pt_t[c], code_t[c]
-                    S1 = syn1[pts]
-                    dot = (S1 * h.unsqueeze(1)).sum(2)
-                    valid = (cds >= 0) & (bag > 0).view(-1, 1) & (dot.abs() < _MAX_EXP)
-                    gsc = ((1 - cds) - torch.sigmoid(dot)) * lr * valid
-                    neu1e = (gsc.unsqueeze(2) * S1).sum(1)
-                    pv = pts[valid]
-                    c1 = (torch.bincount(pv, minlength=syn1.shape[0]).to(h.dtype) / 8).clamp_min(1)
-                    syn1.index_add_(0, pv, (gsc.unsqueeze(2) * h.unsqueeze(1))[valid] / c1[pv].unsqueeze(1))
-                    wi = ctxw[m]
-                    upd = neu1e.unsqueeze(1).expand(-1, m.shape[1], -1)[m]
-                    c0 = (torch.bincount(wi, minlength=syn0.shape[0]).to(h.dtype) / 8).clamp_min(1)
-                    syn0.index_add_(0, wi, upd / c0[wi].unsqueeze(1))
+                    step(syn0, syn1, tb, t_e[idx], t_e[Jc[idx]], m, lr, scratch)
                 processed += n
                 continue
             cen, ctx = [], []
@@ -211,24 +195,11 @@ class H2OWord2vecEstimator(H2OEstimator):
                 lr = max(lr0 * (1 - prog), lr0 * 1e-4)
                 c = t_e[ci[s:s + B]]       # input word (skip-gram: predict centre from context vector)
                 w_in = t_e[xi[s:s + B]]
-                h = syn0[w_in]             # [b, d]
-                pts = pt_t[c]              # [b, L]
-                cds = code_t[c]
-                S1 = syn1[pts]             # [b, L, d]
-                dot = (S1 * h.unsqueeze(1)).sum(2)
-                # hierarchicalSoftmaxSG skips nodes with |f| >= MAX_EXP (6)
-                valid = (cds >= 0) & (dot.abs() < _MAX_EXP)
-                f_ = torch.sigmoid(dot)
-                gsc = ((1 - cds) - f_) * lr * valid
-                neu1e = (gsc.unsqueeze(2) * S1).sum(1)
-                # batched Hogwild: rows hit several times in one batch get the
-                # sum of at most ~8 of their updates (a plain sum overshoots for frequent words)
-                pv = pts[valid]
-                c1 = (torch.bincount(pv, minlength=syn1.shape[0]).to(h.dtype) / 8).clamp_min(1)
-                syn1.index_add_(0, pv, (gsc.unsqueeze(2) * h.unsqueeze(1))[valid] / c1[pv].unsqueeze(1))
-                c0 = (torch.bincount(w_in, minlength=syn0.shape[0]).to(h.dtype) / 8).clamp_min(1)
-                syn0.index_add_(0, w_in, neu1e / c0[w_in].unsqueeze(1))
+                step(syn0, syn1, tb, c, w_in, None, lr, scratch)
             processed += n
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        self._output["w2v_loop_seconds"] = time.perf_counter() - t_loop   # the epochs, without vocabulary / tree set-up
         self._vecs = syn0
         self._output["vocab_size"] = V
         self._output["epochs"] = epochs

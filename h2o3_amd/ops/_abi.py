@@ -58,7 +58,6 @@ _TABLE = {
         h2o_kmeans_assign                  i  PqiPPiPPiP
         h2o_xv                             i  PqiPiPiP
         h2o_kmeans_max_k                   i  ii
-        h2o_kmeans_part_stride             q  ii
         h2o_kmeans_resident_per_cu         i  iiif
         h2o_kmeans_lloyd                   i  PPqiPPiPPPPiifP
         h2o_kmeans_sums_resident_per_cu    i  ii
@@ -131,6 +130,9 @@ _TABLE = {
     "tree_uplift": """
         h2o_uplift_pairs   i  PiiiPPiidiPP
         h2o_uplift_select  i  PPiiiPiPPPPP
+    """,
+    "w2v": """
+        h2o_w2v_hsm_step  i  PPiiiPPPiPPPiifPPPiiiP
     """,
     "tree_split": """
         h2o_split_find_b   i  PiiiPPPdddddiPPiP

@@ -39,6 +39,11 @@ class LloydStats:
     def __init__(self, vec, k, P):
         self.vec, self.k, self.P = vec, k, P
 
+    @staticmethod
+    def stride(k, P):
+        """Length of `vec`, and of one workgroup's partial (km_part_stride in kmeans.hip)."""
+        return k * P + 2 * k + 1
+
     @property
     def sums(self):
         return self.vec[:self.k * self.P].view(self.k, self.P)
@@ -100,7 +105,7 @@ def lloyd_pass(X, C, w=None, assign=None, accumulate=True, dmin=None, use_native
         rows_wg = 64 * (-(-ntiles // _cu_count(X.device)))
         fx = float(2.0 ** 62 / (max(xabs_max, 1e-30) * rows_wg)) if xabs_max > 0 else 1.0
         fx = min(fx, 2.0 ** 100)
-    stride = int(lib.h2o_kmeans_part_stride(k, P))
+    stride = LloydStats.stride(k, P)
     stream = _stream()
     if accumulate and fx > 0 and n_groups is None and _split_ok(lib, k, P, fx):
         return _lloyd_split(lib, X, C32, cn, wt, k, P, ntiles, assign, dmin, xabs_max, stride, stream)

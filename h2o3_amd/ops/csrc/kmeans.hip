@@ -873,8 +873,6 @@ int h2o_kmeans_max_k(int P, int acc) {
   return best;
 }
 
-long long h2o_kmeans_part_stride(int k, int P) { return km_part_stride(k, P); }
-
 // Workgroups of the Lloyd kernel resident per CU for (k, P, acc): the
 // persistent grid is sized to exactly fill the chip (no tail of late
 // workgroups walking a full share of tiles alone).
