@@ -18,8 +18,9 @@ Reference: hex/kmeans/KMeans.java —
   * cluster_size_constraints: the assignment step becomes a transportation
     LP (the reference's KMeansSimplexSolver).
 
-MI355X design: the standardized design matrix is ONE f32 HBM tensor
-[rows, P] (P padded to 4) with each categorical column one-hot encoded at
+MI355X design: the standardized (standardize=False: centred, sigma = 1;
+the f32 distance expansion needs data near the origin) design matrix is
+ONE f32 HBM tensor [rows, P] (P padded to 4) with each categorical column one-hot encoded at
 1/sqrt(2), so the squared euclidean distance of a one-hot block IS the
 reference's 0/1 mismatch; every Lloyd iteration is ONE fused HIP kernel
 pass (ops/csrc/kmeans.hip: f32 MFMA distances, arg-min, LDS per-cluster
@@ -271,8 +272,14 @@ class H2OKMeansEstimator(H2OEstimator):
         p = self._parms
         t0 = time.time()
         t_end = t0 + float(p["max_runtime_secs"]) if float(p.get("max_runtime_secs") or 0) > 0 else None
-        di = DataInfo(spec.frame, spec.x, standardize=bool(p.get("standardize", True)), use_all_factor_levels=True,
-                      pad_to=4)
+        di = DataInfo(spec.frame, spec.x, standardize=True, use_all_factor_levels=True, pad_to=4)
+        # standardize=False: centre only (sigma = 1).  Distances are translation
+        # invariant, but the kernels expand |x|^2 - 2 x.c + |c|^2 in f32, whose
+        # error scales with |x|^2 + |c|^2: the column means are subtracted in
+        # f64 before the f32 store, centers are reported with the mean added back
+        self._center_only = not bool(p.get("standardize", True))
+        if self._center_only:
+            di.sigmas = [1.0] * len(di.sigmas)
         self._dinfo = di
         X, ok = self._design(spec.frame)
         if not bool(ok.all()):
@@ -324,7 +331,12 @@ class H2OKMeansEstimator(H2OEstimator):
         self._scoring_history = hist
         self._train_X, self._train_w = X, w
         self._output["centers"] = self._centers_raw(C)
-        self._output["centers_std"] = C[:, :di.P].cpu().numpy()
+        cs = C[:, :di.P].cpu().numpy()
+        if self._center_only:
+            # not standardized: the design-space centers of raw inputs, as before
+            cs = cs.copy()
+            cs[:, di.n_cat_expanded:] += np.asarray(di.means, dtype=np.float64)
+        self._output["centers_std"] = cs
         self._output["coef_names"] = di.coef_names
         self._output["model_summary"] = {"number_of_rows": nrows_tot, "number_of_clusters": C.shape[0],
                                          "number_of_categorical_columns": len(di.cat_cols),
@@ -346,7 +358,7 @@ class H2OKMeansEstimator(H2OEstimator):
                 elif c in di.num_cols:
                     j = di.num_cols.index(c)
                     v = Ch[r, di.n_cat_expanded + j]
-                    row.append(float(v * di.sigmas[j] + di.means[j]) if di.standardize else float(v))
+                    row.append(float(v * di.sigmas[j] + di.means[j]))
             out.append(row)
         return out
 
@@ -422,9 +434,7 @@ class H2OKMeansEstimator(H2OEstimator):
         di = self._dinfo
         for c in di.cat_cols:
             gc[0, di.cat_offsets[c] + di.cat_modes[c]] = CAT_SCALE
-        if not di.standardize:
-            for j, mu in enumerate(di.means):
-                gc[0, di.n_cat_expanded + j] = mu
+        # numeric columns are centred (standardize=False too): their grand mean is 0
         tot = cluster_ops.lloyd_pass(X, gc, w, accumulate=True)
         coll.allreduce_(tot.vec)
         within = st.withinss.cpu().tolist()

@@ -58,6 +58,7 @@ _TABLE = {
         h2o_kmeans_assign                  i  PqiPPiPPiP
         h2o_xv                             i  PqiPiPiP
         h2o_kmeans_max_k                   i  ii
+        h2o_kmeans_fused_fixed_point       i  ii
         h2o_kmeans_resident_per_cu         i  iiif
         h2o_kmeans_lloyd                   i  PPqiPPiPPPPiifP
         h2o_kmeans_sums_resident_per_cu    i  ii

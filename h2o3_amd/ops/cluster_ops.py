@@ -63,7 +63,9 @@ class LloydStats:
 
 def native_ok(X, k, accumulate=True):
     """The fused kernel takes f32 row-major X with P % 4 == 0, P <= 256 and
-    k up to an LDS-dependent bound (h2o_kmeans_max_k)."""
+    k up to an LDS-dependent bound.  Only the device, dtype and rank are
+    checked here: the guards on P live in h2o_kmeans_max_k (kmeans.hip),
+    which reports 0 for a P it does not serve."""
     if X.device.type != "cuda" or X.dtype != torch.float32 or X.dim() != 2:
         return False
     P = X.shape[1]
@@ -86,8 +88,10 @@ def lloyd_pass(X, C, w=None, assign=None, accumulate=True, dmin=None, use_native
     assignment (changed count) and overwritten with the new one (may be
     None).  dmin: f32 [N] buffer for per-row squared distances to the
     closest center (may be None).  xabs_max: max |w x| (abs_bound) enables
-    the kernel's 64-bit fixed-point cluster sums.  Returns LloydStats
-    (accumulate=True) or None."""
+    the kernel's 64-bit fixed-point cluster sums, which resolve 0.5 / fx per
+    term with fx = 2^62 / (xabs_max * rows per workgroup).  n_groups: grid of
+    the fused kernel (default: the resident workgroups); the scale follows
+    it.  Returns LloydStats (accumulate=True) or None."""
     N, P = X.shape
     k = C.shape[0]
     native = native_ok(X, k, accumulate) if use_native is None else use_native
@@ -101,8 +105,9 @@ def lloyd_pass(X, C, w=None, assign=None, accumulate=True, dmin=None, use_native
     ntiles = (N + 63) // 64
     fx = 0.0
     if accumulate and xabs_max is not None:
-        # per-workgroup |sum| < 2^62 for any grid up to one workgroup per CU
-        rows_wg = 64 * (-(-ntiles // _cu_count(X.device)))
+        # per-workgroup |sum| < 2^62: the default grids below launch at least
+        # min(ntiles, CUs) workgroups; a caller's grid is taken as given
+        rows_wg = 64 * (-(-ntiles // (_cu_count(X.device) if n_groups is None else max(1, int(n_groups)))))
         fx = float(2.0 ** 62 / (max(xabs_max, 1e-30) * rows_wg)) if xabs_max > 0 else 1.0
         fx = min(fx, 2.0 ** 100)
     stride = LloydStats.stride(k, P)

@@ -873,6 +873,14 @@ int h2o_kmeans_max_k(int P, int acc) {
   return best;
 }
 
+// 1 when the fused kernel, given a scale, keeps its per-cluster sums as 64-bit
+// fixed point for (k, P); 0 when their LDS copy does not fit and it falls
+// back to the f32 private copies (km_vrg).
+int h2o_kmeans_fused_fixed_point(int k, int P) {
+  if (P <= 0 || P > 256 || (P & 3) || k <= 0 || k > 256) return 0;
+  return km_vrg(k, P, true, 1.f) == 0 ? 1 : 0;
+}
+
 // Workgroups of the Lloyd kernel resident per CU for (k, P, acc): the
 // persistent grid is sized to exactly fill the chip (no tail of late
 // workgroups walking a full share of tiles alone).
