@@ -23,11 +23,12 @@ from ...core.groupsum import group_sum
 from ...ops import linalg_ops
 
 
-def _kernel_route(X, K):
-    """The fused HIP pass (linalg_ops.glm_multinomial_pass) serves this fit:
+def _kernel_route(X, K, supported=linalg_ops.glm_multinomial_supported):
+    """The fused HIP pass (linalg_ops.glm_multinomial_pass, or glm_ordinal_pass
+    with `supported` = linalg_ops.glm_ordinal_supported) serves this fit:
     a device frame, a shape the kernel holds in LDS, and H2O3_GLM_MULTI not
     set to `torch`.  Asked once per fit."""
-    return (X.is_cuda and X.dtype == torch.float32 and linalg_ops.glm_multinomial_supported(X.shape[1], K)
+    return (X.is_cuda and X.dtype == torch.float32 and supported(X.shape[1], K)
             and os.environ.get("H2O3_GLM_MULTI", "").lower() != "torch")
 
 
@@ -53,9 +54,26 @@ def _loss_grad_multinomial(X, Y, w, B, b0, wsum):
     return float(s[0]) / wsum, s[1:1 + B.numel()].view_as(B) / wsum, s[1 + B.numel():] / wsum
 
 
+def _ordinal_cuts(theta):
+    """theta -> the K-1 ordered cut points (f64): the first value as it is, the
+    later increments through softplus, cumulative sum."""
+    return torch.cumsum(torch.cat([theta[:1], torch.nn.functional.softplus(theta[1:])]), 0)
+
+
+def _loss_grad_ordinal_pass(X, y, w, beta, theta, K):
+    """Kernel route: (loss, gradient over [beta | theta]) as unnormalised local
+    f64 sums from linalg_ops.glm_ordinal_pass.  y: int32 class codes, w: f32.
+    The map theta -> cut points and its chain rule (reverse cumulative sum of
+    g_cuts, times sigmoid(theta) for the softplus increments) stay here in
+    f64, over K-1 numbers."""
+    ll, gb, gc = linalg_ops.glm_ordinal_pass(X, y, w, beta, _ordinal_cuts(theta), K)
+    rc = torch.flip(torch.cumsum(torch.flip(gc, [0]), 0), [0])
+    return ll, torch.cat([gb, rc[:1], rc[1:] * torch.sigmoid(theta[1:])])
+
+
 def _loss_grad_ordinal(X, y, w, beta, theta, wsum, K):
     eta = (X @ beta.to(X.dtype)).to(torch.float64)
-    th = torch.cumsum(torch.cat([theta[:1], torch.nn.functional.softplus(theta[1:])]), 0)
+    th = _ordinal_cuts(theta)
     # P(y<=k) = sigmoid(th_k - eta), k=0..K-2
     cdf = torch.sigmoid(th.view(1, -1) - eta.view(-1, 1))
     cdf = torch.cat([torch.zeros_like(eta).view(-1, 1), cdf, torch.ones_like(eta).view(-1, 1)], 1)
@@ -160,7 +178,10 @@ def fit_multinomial(est, spec, fam):
     """Multinomial / ordinal fit over the lambda path (warm started, GLM.java
     lambda-search early stopping), submodel picked by validation deviance
     when given.  Ordinal coefficients are reported in the reference's
-    parameterisation (P(y <= c) = sigmoid(x.beta + intercept_c))."""
+    parameterisation (P(y <= c) = sigmoid(x.beta + intercept_c)).
+    On the kernel route (_kernel_route) every loss / gradient evaluation of
+    either family is one fused HIP pass; the ordinal GRADIENT_DESCENT_SQERR
+    solver keeps its torch loss, which is a different objective."""
     p = est._parms
     from .interactions import interaction_pairs
     dinfo = DataInfo(spec.frame, spec.x, standardize=bool(p.get("standardize", True)),
@@ -245,15 +266,27 @@ def fit_multinomial(est, spec, fam):
         t0 = torch.log(cum / (1 - cum))
         theta0 = torch.cat([t0[:1], torch.log(torch.expm1((t0[1:] - t0[:-1]).clamp_min(1e-6)))])
         params = torch.cat([null_beta, theta0]).clone()
+        kern = _kernel_route(X, K, linalg_ops.glm_ordinal_supported)
+        # class codes and f32 weights, once per frame
+        codes = {id(y): (y.to(torch.int32), w.to(torch.float32))} if kern else {}
 
         def dev_of(th, Xm, ym, wm, wsm):
-            return 2 * coll.allreduce_scalar(float(_loss_grad_ordinal(Xm, ym, wm, th[:Pp], th[Pp:], wsm, K)[0]))
+            if kern:
+                if id(ym) not in codes:     # the validation frame, converted once
+                    codes[id(ym)] = (ym.to(torch.int32), wm.to(torch.float32))
+                ll = _loss_grad_ordinal_pass(Xm, *codes[id(ym)], th[:Pp], th[Pp:], K)[0]
+            else:
+                ll = _loss_grad_ordinal(Xm, ym, wm, th[:Pp], th[Pp:], wsm, K)[0]
+            return 2 * coll.allreduce_scalar(float(ll))
         null_dev = dev_of(params, X, y, w, wsum)
         # lambda_max from the slope gradient at the intercept-only model
-        t = params.detach().clone().requires_grad_(True)
-        ll, _ = _loss_grad_ordinal(X, y, w, t[:Pp], t[Pp:], wsum, K)
-        ll.backward()
-        g = t.grad[:Pp].clone()
+        if kern:
+            g = _loss_grad_ordinal_pass(X, *codes[id(y)], params[:Pp], params[Pp:], K)[1][:Pp].clone()
+        else:
+            t = params.detach().clone().requires_grad_(True)
+            ll, _ = _loss_grad_ordinal(X, y, w, t[:Pp], t[Pp:], wsum, K)
+            ll.backward()
+            g = t.grad[:Pp].clone()
         coll.allreduce_(g)
         lams = _lambda_path(est, p, float((g / wsum).abs().max()) / max(alpha, 1e-2), alpha, wsum, dinfo.P)
         lmax = lams[0]
@@ -265,12 +298,16 @@ def fit_multinomial(est, spec, fam):
                 params = torch.cat([bi, thi])
             else:
                 def f_g(th, l2=l2):
-                    t = th.detach().clone().requires_grad_(True)
-                    ll, _ = _loss_grad_ordinal(X, y, w, t[:Pp], t[Pp:], wsum, K)
-                    ll = ll / wsum
-                    ll.backward()
-                    g = t.grad.detach()
-                    s = torch.cat([ll.detach().view(1), g])
+                    if kern:
+                        ll, g = _loss_grad_ordinal_pass(X, *codes[id(y)], th[:Pp], th[Pp:], K)
+                        s = torch.cat([ll.view(1), g]) / wsum
+                    else:
+                        t = th.detach().clone().requires_grad_(True)
+                        ll, _ = _loss_grad_ordinal(X, y, w, t[:Pp], t[Pp:], wsum, K)
+                        ll = ll / wsum
+                        ll.backward()
+                        g = t.grad.detach()
+                        s = torch.cat([ll.detach().view(1), g])
                     coll.allreduce_(s)
                     f = float(s[0]) + 0.5 * l2 * float((th[:Pp] ** 2).sum())
                     g = s[1:].clone()

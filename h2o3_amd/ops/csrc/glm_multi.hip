@@ -44,6 +44,46 @@
 // Rows past N are never loaded (their X is zero, their weight 0); rows with
 // w == 0 or a class code outside 0..K-1 get weight 0 and the code is never
 // used as an index.
+//
+// Ordinal (proportional odds, GLMTask.GLMMultinomialGradientBaseTask "ologit")
+// is the second kernel of the file, glm_ordinal_kernel, reached through the
+// same export with Kp == 1 (one shared slope column).  Per row, with cut
+// points c[-1] = -inf < c[0] <= ... <= c[K-2] < c[K-1] = +inf:
+//   eta = x . beta,  a = c[y] - eta,  b = c[y-1] - eta,
+//   pk = sigmoid(a) - sigmoid(b),  loss += -w log(max(pk, 1e-15)),
+//   and, when pk >= 1e-15 (all three are 0 below, as autograd gives through
+//   clamp_min),  d/d eta = w (s'(a) - s'(b)) / pk,  d/d c[y] = -w s'(a) / pk,
+//   d/d c[y-1] = w s'(b) / pk.
+// One output column would leave 15/16 of an MFMA idle: this is a bandwidth
+// kernel on the vector ALUs, one coalesced read of X per evaluation.  The same
+// S slabs, 4 waves and register prefetch ring as above; record
+// [g_beta (Pp) | g_cut (K-1) | loss] of f64, plain stores, fixed-order folds.
+//
+//   LDS   Xs  R x Pp f32 chunk, R = 64 rows to Pp = 256, 32 to 512, 16 to 1024
+//             (a chunk is at most 64 KB and 16 float4 of prefetch per thread;
+//             Pp is a run-time multiple of 4, the row of a chunk element is
+//             found with a float reciprocal).  Both reads of the chunk are
+//             16-byte reads of 4 consecutive columns, across lanes either one
+//             float4 column of 16 consecutive rows (eta) or consecutive float4
+//             of one row (X'd), so instead of the XOR swizzle above the pitch
+//             is an odd number of float4 (Pp or Pp + 4): 16 consecutive rows
+//             fall into the 16 different 4-bank groups.
+//         beta [Pp], cuts [64], eta partials, per-row d, dA, dB, class code.
+//   eta      thread (row = tid % R, part = tid / R) sums x . beta over the
+//            float4 columns part, part + 256 / R, ...; the parts fold through
+//            LDS in part order.  f32 products and sums.
+//   row      lanes 0..R-1 of wave 0 take one row each: two f64 sigmoids from
+//            one exp each, pk (from the complements 1 - sigmoid when both
+//            arguments are positive, which does not cancel against 1), log,
+//            the three derivatives; d/d eta goes to LDS as f32, the cut
+//            derivatives as f64.  y and w of the row are prefetched with X.
+//   g_cut    lane k of every wave owns cut k and adds, in row order, the rows
+//            of the wave's quarter of the chunk that touch it (f64 registers,
+//            no LDS atomics); the four quarters fold once per slab.
+//   X'd      thread (float4 column q = tid % (Pp / 4), row group g) adds
+//            d_r x_r[4q..4q+3] over rows g, g + G, ...: f32 within a chunk,
+//            f64 beyond; the G = min(256 / (Pp / 4), R) row groups fold
+//            through LDS once per slab.
 #include <hip/hip_runtime.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -281,17 +321,238 @@ static int gm_dispatch(int Pp, const float* X, long long N, int ldx, const int* 
   return -1;
 }
 
+// ---------------------------------------------------------------------------
+// Ordinal (proportional odds): one slope column, K - 1 ordered cut points.
+// R rows per chunk, NLD float4 of the next chunk in flight per thread.
+constexpr int GO_PARTS = 4 * GM_THREADS;     // f64 scratch of the final folds: g_beta [G][Pp], G * Pp <= 4 * 256
+constexpr int GO_MISC = GM_THREADS + 6 * 64;  // f32 words: eta partials | dA, dB (f64 [64] each) | d [64] | y [64]
+
+// sigma(t), sigma(-t) and sigma'(t) in f64 from one exp of -|t|; t = +-inf gives (1, 0, 0) / (0, 1, 0).
+__device__ __forceinline__ void go_sigmoid(double t, double& s, double& c, double& ds) {
+  const double e = exp(-fabs(t)), q = 1.0 / (1.0 + e), eq = e * q;
+  s = t >= 0.0 ? q : eq;
+  c = t >= 0.0 ? eq : q;
+  ds = eq * q;
+}
+
+template <int R, int NLD>
+__global__ __launch_bounds__(GM_THREADS) void glm_ordinal_kernel(
+    const float* __restrict__ X, long long N, int Pp, int ldx, const int* __restrict__ y, const float* __restrict__ w,
+    const float* __restrict__ beta, const float* __restrict__ cuts, int K, long long rps, int xs_words,
+    double* __restrict__ part) {
+  constexpr int NP = GM_THREADS / R;         // column parts of the eta step
+  extern __shared__ __align__(16) float gm_lds[];
+  const int C4 = Pp >> 2;                    // float4 per row
+  const int XP = Pp + ((C4 & 1) ? 0 : 4);    // pitch: an odd number of float4
+  float* Xs = gm_lds;                        // [R][XP]; the f64 fold scratch after the last chunk
+  float* bs = Xs + xs_words;                 // beta [Pp]
+  float* cs = bs + Pp;                       // cuts [64]
+  float* ep = cs + 64;                       // eta partials [NP][R]
+  double* dA = (double*)(ep + GM_THREADS);   // d loss / d cuts[y] = -w s'(a) / pk per row
+  double* dB = dA + 64;                      // d loss / d cuts[y-1] = w s'(b) / pk per row
+  float* dsh = (float*)(dB + 64);            // d loss / d eta per row
+  int* ysh = (int*)(dsh + 64);               // class code per row, -2 when the row is dropped
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long row_lo = (long long)blockIdx.x * rps;
+  const long long row_hi = row_lo + rps < N ? row_lo + rps : N;
+
+  for (int i = tid; i < Pp; i += GM_THREADS) bs[i] = beta[i];
+  if (tid < 64) cs[tid] = tid < K - 1 ? cuts[tid] : 0.f;
+
+  // chunk element f = tid + 256 j is float4 c4 of row f / C4; the quotient by a
+  // float reciprocal (f + 0.5 is at least 1 / 512 from an integer multiple of C4)
+  const float inv_c4 = 1.f / (float)C4;
+  const int quads = R * C4;
+  f32x4 pre[NLD];
+  int ypre = -1;                             // lane tid < R: the class and weight of its row of the chunk
+  float wpre = 0.f;
+  auto load = [&](long long base) {
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+      const int f = tid + GM_THREADS * j;
+      const int rr = (int)(((float)f + 0.5f) * inv_c4);
+      const long long r = base + rr;
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      pre[j] = f < quads && r < row_hi ? *(const f32x4*)(X + r * ldx + 4 * (f - rr * C4)) : z;
+    }
+    const bool in = tid < R && base + tid < row_hi;
+    ypre = in ? y[base + tid] : -1;
+    wpre = in ? (w ? w[base + tid] : 1.f) : 0.f;
+  };
+
+  // eta step: row er, float4 columns ept, ept + NP, ...
+  const int er = tid & (R - 1), ept = tid / R;
+  // X'd step: float4 column xq, rows xg, xg + G, ...
+  const int G = GM_THREADS / C4 < R ? GM_THREADS / C4 : R;
+  const int xg = tid / C4, xq = tid - xg * C4;
+  // cut step: lane = cut, rows [R / 4 * wave, R / 4 * (wave + 1))
+  double g64[4] = {0.0, 0.0, 0.0, 0.0}, gc64 = 0.0, loss64 = 0.0;
+
+  if (row_lo < row_hi) load(row_lo);
+  for (long long base = row_lo; base < row_hi; base += R) {
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+      const int f = tid + GM_THREADS * j;
+      const int rr = (int)(((float)f + 0.5f) * inv_c4);
+      if (f < quads) *(f32x4*)(Xs + rr * XP + 4 * (f - rr * C4)) = pre[j];
+    }
+    const int yy = ypre;
+    const float ww = wpre;
+    __syncthreads();
+    if (base + R < row_hi) load(base + R);
+
+    // partial x . beta over this thread's float4 columns
+    {
+      float e = 0.f;
+      const float* xr = Xs + er * XP;
+#pragma unroll 4
+      for (int q = ept; q < C4; q += NP) {
+        const f32x4 xv = *(const f32x4*)(xr + 4 * q), bv = *(const f32x4*)(bs + 4 * q);
+        e += xv[0] * bv[0] + xv[1] * bv[1] + xv[2] * bv[2] + xv[3] * bv[3];
+      }
+      ep[ept * R + er] = e;
+    }
+    __syncthreads();
+
+    // one lane per row: the two sigmoids, pk, loss and the three derivatives in f64
+    if (tid < R) {
+      const bool ok = ww != 0.f && yy >= 0 && yy < K;     // the code of a dropped row is never an index
+      float e = 0.f;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) e += ep[p * R + tid];
+      double dd = 0.0, da = 0.0, db = 0.0;
+      if (ok) {
+        const double eta = (double)e, wd = (double)ww;
+        double sa = 1.0, ca = 0.0, dsa = 0.0, sb = 0.0, cb = 1.0, dsb = 0.0, b = -1.0;
+        if (yy < K - 1) go_sigmoid((double)cs[yy] - eta, sa, ca, dsa);
+        if (yy > 0) {
+          b = (double)cs[yy - 1] - eta;
+          go_sigmoid(b, sb, cb, dsb);
+        }
+        // both arguments positive: the complements do not cancel against 1
+        const double pk = b > 0.0 ? cb - ca : sa - sb;
+        if (pk >= 1e-15) {
+          const double iv = wd / pk;
+          loss64 -= wd * log(pk);
+          dd = (dsa - dsb) * iv;
+          da = -dsa * iv;
+          db = dsb * iv;
+        } else {
+          loss64 -= wd * log(1e-15);
+        }
+      }
+      dsh[tid] = (float)dd;
+      dA[tid] = da;
+      dB[tid] = db;
+      ysh[tid] = ok ? yy : -2;
+    }
+    __syncthreads();
+
+    // g_beta += X'd: f32 over this thread's rows of the chunk, f64 beyond
+    if (xg < G) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      for (int r = xg; r < R; r += G) {
+        const float dr = dsh[r];
+        const f32x4 xv = *(const f32x4*)(Xs + r * XP + 4 * xq);
+        acc[0] += dr * xv[0];
+        acc[1] += dr * xv[1];
+        acc[2] += dr * xv[2];
+        acc[3] += dr * xv[3];
+      }
+#pragma unroll
+      for (int v = 0; v < 4; ++v) g64[v] += (double)acc[v];
+    }
+    // g_cut: the rows of this wave's quarter that touch cut `lane`, in row order
+#pragma unroll 4
+    for (int r = R / 4 * wave; r < R / 4 * (wave + 1); ++r) {
+      const int yr = ysh[r];
+      gc64 += (yr == lane ? dA[r] : 0.0) + (yr - 1 == lane ? dB[r] : 0.0);
+    }
+    __syncthreads();
+  }
+
+  // the slab's record [g_beta (Pp) | g_cut (K - 1) | loss]: row groups, wave
+  // quarters and row lanes folded in a fixed order
+  double* rec = part + (size_t)blockIdx.x * (Pp + K);
+  double* red = (double*)Xs;                 // [G][Pp], then [4][64] cut partials
+  if (xg < G) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) red[xg * Pp + 4 * xq + v] = g64[v];
+  }
+  red[GO_PARTS + tid] = gc64;
+  __syncthreads();
+  for (int c = tid; c < Pp; c += GM_THREADS) {
+    double s = 0.0;
+    for (int q = 0; q < G; ++q) s += red[q * Pp + c];
+    rec[c] = s;
+  }
+  if (tid < K - 1)
+    rec[Pp + tid] = (red[GO_PARTS + tid] + red[GO_PARTS + 64 + tid]) +
+                    (red[GO_PARTS + 128 + tid] + red[GO_PARTS + 192 + tid]);
+  if (wave == 0) {
+    double s = loss64;                       // zero in lanes >= R
+#pragma unroll
+    for (int m = 32; m; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (lane == 0) rec[Pp + K - 1] = s;
+  }
+}
+
+template <int R, int NLD>
+static int go_launch(const float* X, long long N, int Pp, int ldx, const int* y, const float* w, const float* beta,
+                     const float* cuts, int K, int S, long long rps, double* part, hipStream_t s) {
+  const int XP = Pp + (((Pp >> 2) & 1) ? 0 : 4);
+  const int fold = 2 * (GO_PARTS + GM_THREADS);          // f32 words of the f64 fold scratch
+  const int xs_words = R * XP > fold ? R * XP : fold;
+  const size_t lds = sizeof(float) * (size_t)(xs_words + Pp + 64 + GO_MISC);
+  if (lds > 160 * 1024) return -1;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)glm_ordinal_kernel<R, NLD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return (int)hipGetLastError();
+  hipLaunchKernelGGL((glm_ordinal_kernel<R, NLD>), dim3(S), dim3(GM_THREADS), lds, s, X, N, Pp, ldx, y, w, beta, cuts,
+                     K, rps, xs_words, part);
+  return (int)hipGetLastError();
+}
+
+// Chunk rows by width so that a chunk is at most 16 K floats (64 KB of LDS, 16
+// float4 of prefetch per thread): 64 rows to Pp = 256, 32 to 512, 16 to 1024.
+static int go_dispatch(const float* X, long long N, int Pp, int ldx, const int* y, const float* w, const float* beta,
+                       const float* cuts, int K, int S, long long rps, double* part, hipStream_t s) {
+  const int R = Pp <= 256 ? 64 : Pp <= 512 ? 32 : 16;
+  const int nld = (R * (Pp / 4) + GM_THREADS - 1) / GM_THREADS;
+#define GO_CASE(R_, NLD_) \
+  if (R == R_ && nld <= NLD_) return go_launch<R_, NLD_>(X, N, Pp, ldx, y, w, beta, cuts, K, S, rps, part, s)
+  GO_CASE(64, 4);
+  GO_CASE(64, 8);
+  GO_CASE(64, 12);
+  GO_CASE(64, 16);
+  GO_CASE(32, 12);
+  GO_CASE(32, 16);
+  GO_CASE(16, 12);
+  GO_CASE(16, 16);
+#undef GO_CASE
+  return -1;
+}
+
 // X [N, ldx] f32 (columns 0..Pp-1 used, 16-byte aligned rows), y int32 [N],
-// w f32 [N] or null, B [Pp, Kp] f32 and b0 [Kp] f32 (zero past P / K),
-// part [S][Pp * Kp + Kp + 1] f64: every element is written.  S slabs of rps
-// rows (a multiple of 64) cover the N rows.
+// w f32 [N] or null.  S slabs of rps rows (a multiple of 64) cover the N rows.
+// Kp in {16, 32, 64}, multinomial: B [Pp, Kp] f32 and b0 [Kp] f32 (zero past
+//   P / K), part [S][Pp * Kp + Kp + 1] f64.
+// Kp == 1 (one shared slope column), ordinal: B is beta [Pp] f32, b0 the K - 1
+//   ordered cut points f32, part [S][Pp + K] f64 = [g_beta | g_cut | loss].
+// Every element of part is written.
 extern "C" int h2o_glm_multinomial(const float* X, long long N, int Pp, int ldx, const int* y, const float* w,
                                    const float* B, const float* b0, int K, int Kp, int S, long long rps, double* part,
                                    hipStream_t s) {
   if (N <= 0) return 0;
-  if (Pp < 32 || Pp > 256 || Pp % 32 || K < 3 || K > 64 || Kp < K) return -1;
   if (ldx < Pp || ldx % 4 || ((size_t)X & 15) || S <= 0 || rps <= 0 || rps % GM_ROWS || (long long)S * rps < N)
     return -1;
+  if (Kp == 1) {
+    if (Pp < 4 || Pp > 1024 || Pp % 4 || K < 2 || K > 64) return -1;
+    return go_dispatch(X, N, Pp, ldx, y, w, B, b0, K, S, rps, part, s);
+  }
+  if (Pp < 32 || Pp > 256 || Pp % 32 || K < 3 || K > 64 || Kp < K) return -1;
   switch (Kp) {
     case 16: return gm_dispatch<1>(Pp, X, N, ldx, y, w, B, b0, K, S, rps, part, s);
     case 32: return gm_dispatch<2>(Pp, X, N, ldx, y, w, B, b0, K, S, rps, part, s);

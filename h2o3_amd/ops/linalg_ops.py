@@ -347,6 +347,57 @@ def glm_multinomial_pass(X, y, w, B, b0, K, width=None, slabs=None):
     return tot[rec - 1], tot[:Pp * Kp].view(Pp, Kp)[:, :K], tot[Pp * Kp:Pp * Kp + K]
 
 
+def glm_ordinal_supported(width, K):
+    """True when glm_ordinal_pass runs at this padded width and class count
+    (ops/csrc/glm_multi.hip glm_ordinal_kernel: beta and one row chunk of X
+    in LDS, 64 rows to 256 columns, 32 to 512, 16 to 1024)."""
+    width, K = int(width), int(K)
+    return 4 <= width <= 1024 and width % 4 == 0 and 2 <= K <= 64
+
+
+def glm_ordinal_pass(X, y, w, beta, cuts, K, width=None, slabs=None):
+    """One fused pass of the proportional-odds kernel (ops/csrc/glm_multi.hip
+    glm_ordinal_kernel) over the rows of X [N, ldx] f32: per row
+    eta = x . beta, pk = sigmoid(cuts[y] - eta) - sigmoid(cuts[y-1] - eta)
+    (cuts[-1] = -inf, cuts[K-1] = +inf), loss term -w log(max(pk, 1e-15)).
+    Returns (loss, g_beta [Pp], g_cuts [K-1]): f64 device tensors, unnormalised
+    local sums; a row with pk < 1e-15 adds to the loss and to no gradient.
+    y: int32 class codes (a code outside 0..K-1 or w == 0 drops the row),
+    w: f32 or None (all ones), beta [<= Pp] and the K-1 ordered cut points:
+    rounded to f32 here.  `width`: padded width Pp when X is stored wider.
+    `slabs`: number of row slabs (default: about 2048 workgroups of at least
+    64 rows); their f64 records are summed in a fixed order."""
+    N, ldx = X.shape
+    Pp = int(width) if width else ldx
+    K = int(K)
+    if not glm_ordinal_supported(Pp, K):
+        raise ValueError(f"glm_ordinal_pass: width {Pp}, K {K} outside the kernel's range")
+    if X.dtype != torch.float32 or X.stride(1) != 1 or X.stride(0) % 4 or X.data_ptr() % 16:
+        raise ValueError("glm_ordinal_pass: X must be f32, unit column stride, 16-byte aligned rows")
+    if y.dtype != torch.int32 or y.numel() != N or (w is not None and (w.dtype != torch.float32 or w.numel() != N)):
+        raise ValueError("glm_ordinal_pass: y must be int32 [N], w f32 [N] or None")
+    if cuts.numel() != K - 1 or beta.numel() > Pp:
+        raise ValueError("glm_ordinal_pass: K - 1 cut points and at most Pp slopes")
+    bp = torch.zeros(Pp, dtype=torch.float32, device=X.device)
+    bp[:beta.numel()] = beta
+    cp = cuts.to(device=X.device, dtype=torch.float32).contiguous()
+    S = int(slabs) if slabs else max(1, min(2048, N // 64))
+    rps = -(-(-(-N // S)) // 64) * 64
+    S = max(1, -(-N // rps))
+    rec = Pp + K
+    if N == 0:
+        part = torch.zeros((1, rec), dtype=torch.float64, device=X.device)
+    else:
+        part = torch.empty((S, rec), dtype=torch.float64, device=X.device)
+        yc = y.contiguous()
+        wc = None if w is None else w.contiguous()
+        _check(_native.get_lib("glm_multi").h2o_glm_multinomial(
+            _ptr(X), N, Pp, X.stride(0), _ptr(yc), _ptr(wc), _ptr(bp), _ptr(cp), K, 1, S, rps, _ptr(part),
+            _stream()), "h2o_glm_multinomial (ordinal)")
+    tot = part.sum(0)
+    return tot[rec - 1], tot[:Pp], tot[Pp:rec - 1]
+
+
 # Row chunks per batched Gram GEMM (`group`): C_b = hi_b^T [hi_b | lo_b] for g
 # chunks of 512K rows in ONE strided-batched bf16 GEMM (f32 out, each chunk's
 # f32 accumulation stays 512K rows long; chunks summed in f64).  One GEMM per
